@@ -4,6 +4,8 @@
 depth 50, on the MI355X kernels of librtgpu.so.
 
   python bench.py [--gpus N] [--steps K] [--warmup W]     (N > 1: starts its own N ranks, below)
+  python bench.py ... --dump-outputs DIR                  (the last timed frame as DIR/*.npy)
+  python bench.py ... --full                              (+ roofline, CPU baseline, per-pixel check)
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (one rank per GPU)
 
 Without a launcher, `--gpus N` (N > 1) starts `torch.distributed.run --nproc-per-node N` itself as a
@@ -16,10 +18,16 @@ the C-ABI's rtg_gather_rows with --gather-impl rtg). The scene is built and uplo
 (reported separately as setup_ms). value = ray segments traced by all ranks / max-over-ranks wall
 time of the K timed steps. Prints ONE JSON line on rank 0.
 
-Every line carries the per-pixel check of the benchmark frame itself (`parity`: rows of the last timed
+A plain run sets up, warms up, times the K steps, writes the outputs of the last timed step when
+--dump-outputs is given (dump_outputs below) and prints the line. Everything else the benchmark measures
+or checks takes runs of its own and is behind --full: the roofline record (a counting launch of the
+kernel and the PMC records of profiles/), the CPU baseline, the per-pixel check and, at N > 1, the
+cross-check of the product gather.
+
+Every --full line carries the per-pixel check of the benchmark frame itself (`parity`: rows of the last timed
 frame — at N > 1 the frame gathered on rank 0 — against the oracle's fp32 spec on the same seeds).
 N > 1 lines also carry `ranks` (each rank's rows, segments, kernel and gather times, all-gathered
-after timing) and `rtg_gather_check`: after the timed loop, the same shards gathered through the C-ABI's
+after timing) and, with --full, `rtg_gather_check`: after the timed loop, the same shards gathered through the C-ABI's
 own RCCL gather (rtg_comm_create_rank, ranks_seen from ncclCommCount) once per timed step, each call
 timed on the render stream (the product gather's time beside the timed torch gather's, and the library's
 allocations across the calls), the frame compared byte for byte with the timed one, under a watchdog, so a
@@ -77,12 +85,20 @@ def parse():
     ap.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl",
                     help="N>1 process group: nccl (= RCCL, one rank per GPU) or gloo (rehearsal of the N>1 flow "
                          "with several ranks on one GPU; the frame is gathered through host memory)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check what takes runs of its own: the roofline "
+                         "record (counting launch, PMC records), the CPU baseline, the per-pixel check of the last "
+                         "frame against the oracle and, at N>1, the rtg_gather_rows cross-check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all; see dump_outputs)")
     ap.add_argument("--no-rtg-check", action="store_true",
-                    help="N>1: skip the untimed rtg_gather_rows cross-check of the last frame")
+                    help="--full, N>1: skip the untimed rtg_gather_rows cross-check of the last frame")
     ap.add_argument("--check-timeout", type=float, default=180.0,
                     help="N>1: seconds the rtg_gather_rows cross-check may take before the line is printed "
                          "without it")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the CPU legs (cpu_baseline and the per-pixel check)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0,
                     help="wall time the all-cores CPU sample is sized for (the 1-core sample adds ~3-5 s)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = every core of the host (cgroup quota bound)")
@@ -272,6 +288,43 @@ def pmc_binding(workload, kernel_s, plan):
     return rec
 
 
+DUMP_LIMIT = 64 << 20  # bytes --dump-outputs may write in all
+DUMP_SAMPLE_SEED = 0x0D5EED
+
+
+def dump_rows(H, row_bytes, limit=DUMP_LIMIT):
+    """The rows of an H-row frame that --dump-outputs writes, ascending: every row where the frame fits
+    in `limit` bytes (row_bytes = one row of every dumped array as written, plus 8 for its index),
+    else as many as fit, drawn once from a fixed seed (the same rows in every run and every build)."""
+    import numpy as np
+
+    n = max(1, min(H, (limit - 4096) // row_bytes))  # 4 KiB: the .npy headers and segments.npy
+    if n >= H:
+        return np.arange(H)
+    return np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(H, size=n, replace=False))
+
+
+def dump_outputs(dirpath, frames, segments):
+    """--dump-outputs: what a caller of the timed path holds after the last timed step, as .npy files.
+      frame.npy       rows of the linear fp32 frame (at N > 1 the frame gathered on rank 0; with --gather
+                      rgb8 at N > 1 that frame is the write_color bytes), float32 (rows, W, 3)
+      frame_rgb8.npy  N = 1 with --gather rgb8: the write_color bytes rtg_resolve_rgb8 made of it, float32
+      frame_rows.npy  the image row of each dumped row, float64 (all rows unless the frame exceeds the
+                      64 MB budget: dump_rows)
+      segments.npy    ray segments rank 0 traced in that step (rtg_render_stats.segments), float64 (1,)
+    `frames` maps a name to a host array of H rows."""
+    import numpy as np
+
+    os.makedirs(dirpath, exist_ok=True)
+    H = next(iter(frames.values())).shape[0]
+    row_bytes = sum(int(np.prod(f.shape[1:])) * 4 for f in frames.values()) + 8
+    rows = dump_rows(H, row_bytes)
+    for name, f in frames.items():
+        np.save(os.path.join(dirpath, name + ".npy"), np.ascontiguousarray(f[rows], dtype=np.float32))
+    np.save(os.path.join(dirpath, "frame_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(dirpath, "segments.npy"), np.array([segments], dtype=np.float64))
+
+
 class _Watchdog:
     """Runs fn() in this thread; if it has not returned after `seconds`, on_timeout() runs on a timer
     thread (it prints the line and ends the process: a hang in an optional check must not lose it)."""
@@ -439,14 +492,20 @@ def main():
         dist.barrier()
     dt = time.perf_counter() - t0
     gather_ms = [a.elapsed_time(b_) for a, b_ in gev] if world > 1 else []
-    # host copy of the last timed frame (seed args.seed + warmup + steps - 1), for the per-pixel check
-    want_parity = not args.no_cpu_baseline and args.parity_seconds > 0
+    # host copy of the last timed frame (seed args.seed + warmup + steps - 1), for --dump-outputs and the
+    # per-pixel check
+    want_parity = args.full and not args.no_cpu_baseline and args.parity_seconds > 0
     last_frame = None
-    if want_parity:
+    if want_parity or args.dump_outputs:
         if world == 1:
             last_frame = shard[:H].cpu().numpy()
         elif rank == 0 and gathered[0] is not None:
             last_frame = gathered[0].cpu().numpy()
+    if args.dump_outputs and last_frame is not None:
+        frames = {"frame": last_frame}
+        if world == 1 and shard8 is not None:
+            frames["frame_rgb8"] = shard8[:H].cpu().numpy()
+        dump_outputs(args.dump_outputs, frames, int(st.segments) if st is not None else 0)
 
     tot = torch.tensor([float(segs)], dtype=torch.float64, device="cpu" if gloo else "cuda")
     tmax = torch.tensor([dt], dtype=torch.float64, device="cpu" if gloo else "cuda")
@@ -455,16 +514,18 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     total_segs, wall = float(tot.item()), float(tmax.item())
 
-    # algorithmic bytes of one launch (counting variant of the same kernel, same seed, untimed)
-    cst = (ds.render_device(cam, shard.data_ptr(), stream, seed=args.seed + args.warmup, row_begin=b,
-                            row_stride=stride, row_count=n, count=True) if n > 0 else rtgpu.rtg_render_stats())
-    algo_bytes = (BYTES_PER_BOX * cst.box_tests + BYTES_PER_PRIM * cst.prim_tests
-                  + BYTES_PER_HIT * cst.hits)
     avg_kernel_s = max(sum(kernel_ms) / len(kernel_ms) / 1e3, 1e-9)
-    achieved = algo_bytes / avg_kernel_s / 1e9
     workload = (f"{args.scene}(grid={args.grid}) {W}x{H} {args.spp}spp depth{args.depth} bvh={args.bvh} "
                 f"chunk={rtgpu.chunk_samples(args.spp)}")
-    traffic = pmc_traffic(workload) if world == 1 else None
+    cst, algo_bytes, achieved, traffic = None, 0, 0.0, None
+    if args.full:
+        # algorithmic bytes of one launch (counting variant of the same kernel, same seed, untimed)
+        cst = (ds.render_device(cam, shard.data_ptr(), stream, seed=args.seed + args.warmup, row_begin=b,
+                                row_stride=stride, row_count=n, count=True) if n > 0 else rtgpu.rtg_render_stats())
+        algo_bytes = (BYTES_PER_BOX * cst.box_tests + BYTES_PER_PRIM * cst.prim_tests
+                      + BYTES_PER_HIT * cst.hits)
+        achieved = algo_bytes / avg_kernel_s / 1e9
+        traffic = pmc_traffic(workload) if world == 1 else None
     setup_ms = {"scene_build_ms": round(t_scene * 1e3, 1), "scene_create_ms": round(t_create * 1e3, 1),
                 "host_compile_ms": round(info.build_ms, 1), "bvh_ms": round(info.bvh_ms, 1),
                 "collapse_ms": round(info.collapse_ms, 1), "flatten_ms": round(info.flatten_ms, 1),
@@ -488,7 +549,7 @@ def main():
                "frac": round(achieved / LDS_PEAK_GBS, 4),
                "note": "the same algorithmic bytes against the ds_read_b128 aggregate (MI355X_MICROARCH.md "
                        "§LDS): the scene is LDS-resident for configs 2-4 (config 5: the top of the tree)"}
-        binding = pmc_binding(workload, avg_kernel_s, plan) if world == 1 else None
+        binding = pmc_binding(workload, avg_kernel_s, plan) if world == 1 and args.full else None
         line = {
             "metric": METRIC,
             "value": round(total_segs / wall / 1e6, 3),
@@ -510,7 +571,10 @@ def main():
                                        f"{'rtg_gather_rows' if args.gather_impl == 'rtg' else 'torch.distributed'}) "
                                        f"of the frame to rank 0 per step" if world > 1 else
                                        "1 GPU, whole frame (no gather)")},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
+            "full": bool(args.full),
+            # the roofline record needs the counting launch: None in a plain run
+            "roofline": None if cst is None else
+                        {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
                          "traffic": traffic,
                          "traffic_gbs": (round(traffic / avg_kernel_s / 1e9, 2) if traffic else None),
@@ -550,7 +614,7 @@ def main():
             line["ranks"] = ranks
             line["gather_ms"] = [r["gather_ms"] for r in ranks]
             line["kernel_ms_per_rank"] = [r["kernel_ms"] for r in ranks]
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args, s.desc, cam)
             cb = line["cpu_baseline"]
             line["speedup_vs_cpu"] = round(line["value"] / cb["value"], 1) if cb["value"] else None
@@ -564,7 +628,7 @@ def main():
                 lin = cb["one_core"]["value"] * online
                 line["speedup_vs_cpu_all_host_cores_linear"] = {
                     "cores": online, "cpu_value": round(lin, 1), "speedup": round(line["value"] / lin, 1)}
-        if last_frame is not None:
+        if want_parity and last_frame is not None:
             cores = host_cpus()[0]
             cb = line["cpu_baseline"]
             # rows sized for ~parity_seconds on the cores at the measured one-core rate (the fp32 spec
@@ -583,7 +647,7 @@ def main():
             if world > 1:
                 line["parity"]["frame"] = f"gathered on rank 0 from {world} ranks"
 
-    if world > 1 and not args.no_rtg_check and not gloo:
+    if args.full and world > 1 and not args.no_rtg_check and not gloo:
         # the C-ABI's RCCL gather, outside the timed region, on the last frame's shards, once per timed step:
         # its per-call time beside the timed torch gather's, and byte-compared with the timed frame
         def give_up():

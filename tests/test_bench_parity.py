@@ -37,6 +37,42 @@ def test_cpu_parity_against_the_oracle(scenes, oracle):
     assert not off["pass"]
 
 
+def test_plain_run_is_the_default(monkeypatch):
+    """--full (roofline, CPU baseline, per-pixel check, gather cross-check) and --dump-outputs are off
+    unless asked for."""
+    import sys
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (3, 1)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_rows_are_fixed_and_within_the_budget():
+    """--dump-outputs writes every row of a frame that fits the 64 MB budget (config 2: 24.9 MB), else a
+    fixed sample of its rows: the same rows every time, ascending, distinct, as many as fit."""
+    assert np.array_equal(bench.dump_rows(1080, 1920 * 12 + 8), np.arange(1080))
+    row_bytes = 3840 * 12 + 8  # config 5: 99.5 MB of frame
+    rows = bench.dump_rows(2160, row_bytes)
+    assert np.array_equal(rows, bench.dump_rows(2160, row_bytes))
+    assert len(rows) == (bench.DUMP_LIMIT - 4096) // row_bytes < 2160
+    assert np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < 2160
+    assert len(bench.dump_rows(5, 100, limit=10)) == 1  # never empty
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    frame = np.arange(7 * 5 * 3, dtype=np.float32).reshape(7, 5, 3)
+    rgb8 = (np.arange(7 * 5 * 3) % 256).astype(np.uint8).reshape(7, 5, 3)
+    bench.dump_outputs(str(tmp_path / "d"), {"frame": frame, "frame_rgb8": rgb8}, 1234567)
+    got = {n: np.load(tmp_path / "d" / f"{n}.npy") for n in ("frame", "frame_rgb8", "frame_rows", "segments")}
+    assert got["frame"].dtype == np.float32 and np.array_equal(got["frame"], frame)
+    assert got["frame_rgb8"].dtype == np.float32 and np.array_equal(got["frame_rgb8"], rgb8)
+    assert got["frame_rows"].dtype == np.float64 and np.array_equal(got["frame_rows"], np.arange(7))
+    assert got["segments"].dtype == np.float64 and got["segments"].tolist() == [1234567.0]
+
+
 def _args(gpus):
     import types
     return types.SimpleNamespace(gpus=gpus)

@@ -1391,7 +1391,7 @@ def test_bench_two_ranks_rehearsal(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(REPO, "bench.py"),
            "--gpus", "2", "--dist-backend", "gloo", "--width", "192", "--height", "108", "--spp", "8",
-           "--depth", "10", "--steps", "2", "--warmup", "1", "--parity-seconds", "1"]
+           "--depth", "10", "--steps", "2", "--warmup", "1", "--full", "--parity-seconds", "1"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -1416,7 +1416,7 @@ def test_bench_launches_its_own_ranks(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
            "--width", "160", "--height", "90", "--spp", "4", "--depth", "8", "--steps", "1", "--warmup", "1",
-           "--parity-seconds", "1"]
+           "--full", "--parity-seconds", "1"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=str(tmp_path), env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -1425,6 +1425,35 @@ def test_bench_launches_its_own_ranks(tmp_path):
     assert line["n_gpus"] == 2 and [x["rank"] for x in line["ranks"]] == [0, 1]
     assert [x["rows"] for x in line["ranks"]] == [45, 45]
     assert line["parity"]["pass"] and line["parity"]["identical_frac"] > 0.999, line["parity"]
+
+
+def test_bench_plain_run_dumps_its_last_frame(tmp_path, scenes, oracle):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times its K steps and nothing else: the line says
+    so (`full` false, no roofline record, CPU baseline or per-pixel check), and `--dump-outputs DIR` leaves
+    the last timed frame (seed + W + K - 1) there as float32, every row of it at this size: the oracle's
+    frame on that seed (north star: RMSE < 1e-3), with that step's segment count."""
+    import json
+    import sys
+
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--width", "160", "--height", "90", "--spp", "4", "--depth", "8", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["full"] is False and line["steps"] == 2 and line["warmup"] == 1 and line["n_gpus"] == 1
+    assert line["unit"] == "Mrays/s" and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["roofline"] is None and line["cpu_baseline"] is None and "parity" not in line
+    frame, rows, segs = (np.load(out / f"{k}.npy") for k in ("frame", "frame_rows", "segments"))
+    assert frame.dtype == np.float32 and frame.shape == (90, 160, 3)
+    assert rows.dtype == np.float64 and np.array_equal(rows, np.arange(90))
+    s = scenes.build("bouncing_spheres", grid=11, image_width=160, aspect_ratio=160 / 90, spp=4, max_depth=8,
+                     rand_seed=1)
+    ref, ref_segs = oracle.render_f32(s.desc, s.camera, seed=0x5EED + 2)
+    assert np.all(np.isfinite(frame)) and rmse(frame, ref) < RMSE_TOL
+    assert segs.dtype == np.float64 and abs(int(segs[0]) - int(ref_segs)) <= max(2, 1e-4 * ref_segs)
 
 
 def test_numerics_helpers_match_ieee():

@@ -18,6 +18,6 @@ step smoke 400 python3 -c "import __graft_entry__ as g; g.smoke()" || exit $?
 step gpu_tests 1200 python3 -m pytest tests -m gpu -q -rf --timeout 600
 rc=$?
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
-step bench 900 python3 bench.py "$@" || exit $?
+step bench 900 python3 bench.py --full "$@" || exit $?
 grep '^{' gpurun_out/bench.log > gpurun_out/bench.json
 exit 0

@@ -24,7 +24,7 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
   [ $rc -ne 0 ] && exit $rc
 fi
 for c in $CONFIGS; do
-  step bench_config$c 900 python3 bench.py --config "$c" ${BENCH_ARGS:-} || exit $?
+  step bench_config$c 900 python3 bench.py --full --config "$c" ${BENCH_ARGS:-} || exit $?
   grep '^{' "$OUT/bench_config$c.log" > "$OUT/bench_config$c.json"
 done
 exit 0
