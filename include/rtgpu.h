@@ -41,14 +41,19 @@ typedef int32_t rtg_status;
 /* ---- primitives: replaces sphere (sphere.hpp:16-23, 32-44) and quad (quad.hpp:12-27) ---- */
 #define RTG_PRIM_SPHERE 1
 #define RTG_PRIM_QUAD 2
+/* The triangle with vertices Q, Q + u, Q + v: the planar shape the reference's virtual quad::is_interior
+ * (quad.hpp:97) is there for, inside where a >= 0 && b >= 0 && a + b <= 1. Everything else as a quad: the
+ * same plane and t, the same exact-t tie rule, (u, v) of the hit record = (a, b). A triangle with
+ * |u x v| == 0 is RTG_E_INVALID. Additive in ABI 7. */
+#define RTG_PRIM_TRIANGLE 3
 
 typedef struct rtg_primitive {
-  int32_t kind;     /* RTG_PRIM_SPHERE | RTG_PRIM_QUAD */
+  int32_t kind;     /* RTG_PRIM_SPHERE | RTG_PRIM_QUAD | RTG_PRIM_TRIANGLE */
   int32_t material; /* index into rtg_scene_desc.materials */
-  double p0[3];     /* sphere: centre at time 0 (ray center.orig) | quad: Q */
-  double p1[3];     /* sphere: centre at time 1 (static: == p0)   | quad: u */
-  double p2[3];     /* sphere: unused                             | quad: v */
-  double radius;    /* sphere radius (sign kept, as the reference allows) */
+  double p0[3];     /* sphere: centre at time 0 (ray center.orig) | quad, triangle: Q */
+  double p1[3];     /* sphere: centre at time 1 (static: == p0)   | quad, triangle: u */
+  double p2[3];     /* sphere: unused                             | quad, triangle: v */
+  double radius;    /* sphere radius (sign kept, as the reference allows); unused otherwise */
 } rtg_primitive;
 
 /* ---- materials: replaces material.hpp:42-75, 80-111, 122-207, 223-240 ---- */

@@ -188,6 +188,9 @@ int host_threads(int64_t n) {
 // - other quads, every axis: eta = 2^-18 (|v| + M): their float normal and plane distance are rounded, so
 //   the accepted points leave the corners' box by a few 2^-24 (|v| + M) plus 2^-24 of the distance
 //   (<= |v| + 2M), all taken in the pad.
+// - triangles, every axis: the pad of the other quads, 2^-18 (|v| + M): their records are rounded plane forms
+//   too (normal, plane distance, the two edge planes), so the points they accept leave the three vertices' box
+//   by a few 2^-24 (|v| + M) plus 2^-24 of the distance, as for a general quad.
 // The flat axis of an axis-aligned quad (u and v each along one coordinate axis, so the record's normal is
 // exactly +-e_k, its plane distance +-Q_k, and alpha / beta each depend on one coordinate of the hit point),
 // or -1.
@@ -458,9 +461,16 @@ bool compile_scene(const rtg_scene_desc* d, HostScene* out, std::string* err) {
   }
   for (int64_t i = 0; i < d->num_prims; ++i) {
     const rtg_primitive& p = d->prims[i];
-    if (p.kind != RTG_PRIM_SPHERE && p.kind != RTG_PRIM_QUAD) {
+    if (p.kind != RTG_PRIM_SPHERE && p.kind != RTG_PRIM_QUAD && p.kind != RTG_PRIM_TRIANGLE) {
       *err = "unknown primitive kind at index " + std::to_string(i);
       return false;
+    }
+    if (p.kind == RTG_PRIM_TRIANGLE) {  // |u x v| == 0: no plane
+      const D3 n = cross(d3(p.p1), d3(p.p2));
+      if (!(dot(n, n) > 0.0)) {
+        *err = "degenerate triangle (|u x v| == 0) at index " + std::to_string(i);
+        return false;
+      }
     }
     if (p.material < 0 || p.material >= d->num_materials) {
       *err = "primitive material index out of range at index " + std::to_string(i);
@@ -623,7 +633,11 @@ bool compile_scene(const rtg_scene_desc* d, HostScene* out, std::string* err) {
 
   // primitives, laid out in first-reference order for locality
   std::vector<int32_t> slot(d->num_prims, -1);
-  int32_t nsph = 0, nquad = 0;
+  int32_t nsph = 0, nquad = 0, ntri = 0;
+  if (d->num_prims >= kTriRefBit) {  // slots share a ref with the kind bits (kQuadRefBit, kTriRefBit)
+    *err = "too many primitives (slot counts must stay below 2^29)";
+    return false;
+  }
   out->refs.resize(bvh.refs.size());
   for (size_t r = 0; r < bvh.refs.size(); ++r) {
     const int64_t pid = bvh.refs[r];
@@ -640,6 +654,31 @@ bool compile_scene(const rtg_scene_desc* d, HostScene* out, std::string* err) {
                               static_cast<float>(p.p1[2] - p.p0[2]),
                               ibits_to_float(p.material)};
         out->spheres.insert(out->spheres.end(), rec, rec + 8);
+      } else if (p.kind == RTG_PRIM_TRIANGLE) {
+        slot[pid] = ntri++;
+        // the quad constructor's plane (quad.hpp:12-27) and the two edge planes of the inside test, in fp64,
+        // then rounded: alpha = w . (hp x v) = A . p + a0 with A = v x w, a0 = -A . Q; beta = w . (u x hp) =
+        // B . p + b0 with B = w x u, b0 = -B . Q (hp = p - Q)
+        const D3 Q = d3(p.p0), u = d3(p.p1), v = d3(p.p2);
+        const D3 n = cross(u, v);
+        const D3 normal = unit_vector(n);
+        const double D = dot(normal, Q);
+        const D3 w = n / dot(n, n);
+        const D3 A = cross(v, w), B = cross(w, u);
+        const float rec[12] = {static_cast<float>(normal.x), static_cast<float>(normal.y), static_cast<float>(normal.z),
+                               static_cast<float>(D),        static_cast<float>(A.x),      static_cast<float>(A.y),
+                               static_cast<float>(A.z),      static_cast<float>(-dot(A, Q)), static_cast<float>(B.x),
+                               static_cast<float>(B.y),      static_cast<float>(B.z),      static_cast<float>(-dot(B, Q))};
+        out->tris.insert(out->tris.end(), rec, rec + 12);
+        out->tri_meta.push_back(p.material);
+        out->tri_meta.push_back(static_cast<int32_t>(tie_rank(pid)));
+        if (gpu_bvh) {  // the device builder's view of the triangle: its vertex box
+          double lo[3], hi[3];
+          prim_bbox(p, lo, hi);
+          const float b6[6] = {round_down(lo[0]), round_down(lo[1]), round_down(lo[2]),
+                               round_up(hi[0]),   round_up(hi[1]),   round_up(hi[2])};
+          out->tri_boxes.insert(out->tri_boxes.end(), b6, b6 + 6);
+        }
       } else {
         slot[pid] = nquad++;
         // quad ctor (quad.hpp:12-27) in fp64, then rounded; the v row's 4th word holds the quad's tie
@@ -662,7 +701,9 @@ bool compile_scene(const rtg_scene_desc* d, HostScene* out, std::string* err) {
         out->quads.insert(out->quads.end(), rec, rec + 20);
       }
     }
-    out->refs[r] = (p.kind == RTG_PRIM_QUAD) ? (slot[pid] | kQuadRefBit) : slot[pid];
+    out->refs[r] = p.kind == RTG_PRIM_QUAD       ? (slot[pid] | kQuadRefBit)
+                   : p.kind == RTG_PRIM_TRIANGLE ? (slot[pid] | kTriRefBit)
+                                                 : slot[pid];
   }
   if (out->occluder_prim >= 0) {  // after every referenced sphere, so the refs stay the identity
     const rtg_primitive& p = d->prims[out->occluder_prim];
@@ -675,10 +716,11 @@ bool compile_scene(const rtg_scene_desc* d, HostScene* out, std::string* err) {
     out->spheres.insert(out->spheres.end(), rec, rec + 8);
   }
 
-  // the exact-t tie rule's order: tie rank per sphere slot, then per quad slot
+  // the exact-t tie rule's order: tie rank per sphere slot, then per quad slot (a triangle's
+  // is in its cold record)
   out->tie_rank.assign(static_cast<size_t>(nsph) + nquad, -1);
   for (int64_t i = 0; i < d->num_prims; ++i)
-    if (slot[i] >= 0)
+    if (slot[i] >= 0 && d->prims[i].kind != RTG_PRIM_TRIANGLE)
       out->tie_rank[(d->prims[i].kind == RTG_PRIM_QUAD ? nsph : 0) + slot[i]] = static_cast<int32_t>(tie_rank(i));
   phase("prims");
   // culling boxes (the margin above) in place of the reference's, then rounded outward
@@ -1066,6 +1108,10 @@ rtg_status rtg_scene_create(const rtg_scene_desc* desc_in, int32_t device, rtg_s
   total += (hs.perlin_perm.size() * 4 + 255) & ~size_t(255);
   const size_t rank_off = total;
   total += (hs.tie_rank.size() * 4 + 255) & ~size_t(255);
+  const size_t tris_off = total;  // the triangles' hot records, then their cold records
+  total += (hs.tris.size() * 4 + 255) & ~size_t(255);
+  const size_t tri_meta_off = total;
+  total += (hs.tri_meta.size() * 4 + 255) & ~size_t(255);
   total = std::max<size_t>(total, 256);
 
   rtg_scene* s = new (std::nothrow) rtg_scene();
@@ -1101,6 +1147,8 @@ rtg_status rtg_scene_create(const rtg_scene_desc* desc_in, int32_t device, rtg_s
       if (p.bytes != 0 && p.src) srcs.push_back({p.src, p.bytes, p.off});
     if (!hs.perlin_perm.empty()) srcs.push_back({hs.perlin_perm.data(), hs.perlin_perm.size() * 4, perm_off});
     if (!hs.tie_rank.empty()) srcs.push_back({hs.tie_rank.data(), hs.tie_rank.size() * 4, rank_off});
+    if (!hs.tris.empty()) srcs.push_back({hs.tris.data(), hs.tris.size() * 4, tris_off});
+    if (!hs.tri_meta.empty()) srcs.push_back({hs.tri_meta.data(), hs.tri_meta.size() * 4, tri_meta_off});
     size_t end = 0;
     for (const Src& x : srcs) end = std::max(end, x.off + x.bytes);
     void* stage = nullptr;
@@ -1129,15 +1177,27 @@ rtg_status rtg_scene_create(const rtg_scene_desc* desc_in, int32_t device, rtg_s
     int32_t* sorted = nullptr;
     if ((e = dev_alloc_async(reinterpret_cast<void**>(&sorted), nrefs * 4, s->own_stream)) != hipSuccess)
       return cleanup(hip_fail(e, "hipMalloc(bvh refs)"));
+    // the triangles' vertex boxes, for the build only (their plane-form records do not hold the vertices)
+    float* tri_boxes = nullptr;
+    if (!hs.tri_boxes.empty()) {
+      e = dev_alloc_async(reinterpret_cast<void**>(&tri_boxes), hs.tri_boxes.size() * 4, s->own_stream);
+      if (e == hipSuccess)
+        e = hipMemcpyAsync(tri_boxes, hs.tri_boxes.data(), hs.tri_boxes.size() * 4, hipMemcpyHostToDevice, s->own_stream);
+      if (e != hipSuccess) return cleanup(hip_fail(e, "hipMalloc(triangle boxes)"));
+    }
     GpuBvhResult r{};
     e = gpu_build_bvh4(reinterpret_cast<const float4*>(base + parts[2].off),
-                       reinterpret_cast<const float4*>(base + parts[3].off), refs_dev, nrefs,
+                       reinterpret_cast<const float4*>(base + parts[3].off), tri_boxes, refs_dev, nrefs,
                        round_up(hs.origin_bound), reinterpret_cast<float*>(base + parts[0].off),
                        hs.node_capacity, sorted, &r, s->own_stream);
     if (e == hipSuccess)
       e = hipMemcpyAsync(refs_dev, sorted, nrefs * 4, hipMemcpyDeviceToDevice, s->own_stream);
     const hipError_t ef = hipFreeAsync(sorted, s->own_stream);
     if (e == hipSuccess) e = ef;
+    if (tri_boxes) {
+      const hipError_t et = hipFreeAsync(tri_boxes, s->own_stream);
+      if (e == hipSuccess) e = et;
+    }
     if (e == hipSuccess) e = hipStreamSynchronize(s->own_stream);
     if (e != hipSuccess) return cleanup(hip_fail(e, "device BVH build"));
     hs.num_nodes = r.num_nodes;
@@ -1162,6 +1222,9 @@ rtg_status rtg_scene_create(const rtg_scene_desc* desc_in, int32_t device, rtg_s
   s->dev.perlin_vec = reinterpret_cast<const float4*>(base + parts[8].off);
   s->dev.perlin_perm = reinterpret_cast<const uint32_t*>(base + perm_off);
   s->dev.tie_rank = reinterpret_cast<const int32_t*>(base + rank_off);
+  s->dev.tris = reinterpret_cast<const float4*>(base + tris_off);
+  s->dev.tri_meta = reinterpret_cast<const int2*>(base + tri_meta_off);
+  s->dev.num_tris = static_cast<int64_t>(hs.tris.size() / 12);
   s->dev.num_nodes = hs.num_nodes;
   s->dev.root_code = 0;
   s->dev.occluder = hs.occluder;
@@ -1178,12 +1241,13 @@ rtg_status rtg_scene_create(const rtg_scene_desc* desc_in, int32_t device, rtg_s
   s->dev.num_textures = static_cast<int32_t>(hs.textures.size() / 8);
   s->dev.ref_mode = 0;
   {
-    bool ident_s = !hs.refs.empty(), ident_q = !hs.refs.empty();
-    for (size_t r = 0; r < hs.refs.size() && (ident_s || ident_q); ++r) {
+    bool ident_s = !hs.refs.empty(), ident_q = !hs.refs.empty(), ident_t = !hs.refs.empty();
+    for (size_t r = 0; r < hs.refs.size() && (ident_s || ident_q || ident_t); ++r) {
       ident_s = ident_s && hs.refs[r] == static_cast<int32_t>(r);
       ident_q = ident_q && hs.refs[r] == (static_cast<int32_t>(r) | kQuadRefBit);
+      ident_t = ident_t && hs.refs[r] == (static_cast<int32_t>(r) | kTriRefBit);
     }
-    s->dev.ref_mode = ident_s ? 1 : (ident_q ? 2 : 0);
+    s->dev.ref_mode = ident_s ? 1 : (ident_q ? 2 : (ident_t ? 3 : 0));
     if (hs.gpu_bvh) s->dev.ref_mode = 0;  // the device build permuted the refs
   }
   s->dev.tex_full = 0;
@@ -1450,8 +1514,13 @@ rtg_status plan_render(const rtg_scene* s, const rtg_camera_desc* cam, const rtg
   // (first primitive < 4096) and whose node array ends below 32 KB of LDS (inner codes are absolute LDS
   // addresses) and whose stack needs no spill (kernel LdsStack16), else 32-bit
   const bool lds_entries_knob = K.stack_lds_entries > 0;
-  const bool stk16 = dscene.node_width == 4 && dscene.num_refs <= 4096 && dscene.num_nodes * 112 <= 32768 &&
-                     need <= kLdsStack && !lds_entries_knob && !dscene.tex_full;
+  const bool stk16_fits = dscene.node_width == 4 && dscene.num_refs <= 4096 && dscene.num_nodes * 112 <= 32768 &&
+                          need <= kLdsStack && !lds_entries_knob && !dscene.tex_full;
+  // triangles: a triangle-only scene (ref_mode 3) on the 16-bit-stack layout runs the triangle-only kernel class;
+  // any other scene with triangles the mixed kernels built with the triangle branch, which exist in one shape per
+  // schedule (16-wave workgroups, 32-bit stack entries, no dual launch; rtg_kernels.hip default_kernel)
+  const bool tri_mix = dscene.num_tris > 0 && !(dscene.ref_mode == 3 && stk16_fits);
+  const bool stk16 = stk16_fits && !tri_mix;
   dj.stack_esz = stk16 ? 2 : 4;
   dj.lds_waves = kLdsWaves;
   int lds_bytes = lds_layout(dscene, kLdsStack, kLdsWaves, dj.stack_esz, &dj);
@@ -1460,7 +1529,8 @@ rtg_status plan_render(const rtg_scene* s, const rtg_camera_desc* cam, const rtg
     DevJob t = dj;
     const int b4 = lds_layout(dscene, kLdsStack, 4, dj.stack_esz, &t);
     if ((K.lds_waves == 0 || K.lds_waves == 4) && dscene.node_width == 4 && need <= kLdsStack &&
-        !lds_entries_knob && b4 > 0 && lds_alloc(b4) * kSmallSceneWgs <= kLdsPerCu && (stk16 || dscene.tex_full)) {
+        !lds_entries_knob && b4 > 0 && lds_alloc(b4) * kSmallSceneWgs <= kLdsPerCu && (stk16 || dscene.tex_full) &&
+        !tri_mix) {
       dj = t;
       dj.lds_waves = 4;
       lds_bytes = b4;
@@ -1565,13 +1635,15 @@ rtg_status plan_render(const rtg_scene* s, const rtg_camera_desc* cam, const rtg
   if (P->skip_kernel || variant != 3) lds4 = -1;
   if (lds4 > 0) {  // the dual launch's job: the same frame, counters and buffers as dj
     const int32_t l4[] = {j4.lds_nodes, j4.lds_refs, j4.lds_spheres, j4.lds_quads, j4.lds_materials,
-                          j4.lds_textures, j4.lds_perlin_vec, j4.lds_perlin_perm, j4.lds_stacks, j4.lds_ring};
+                          j4.lds_textures, j4.lds_perlin_vec, j4.lds_perlin_perm, j4.lds_stacks, j4.lds_ring,
+                          j4.lds_tris, j4.lds_tri_meta};
     j4 = dj;
     j4.lds_waves = 4;
     j4.lds_nodes = l4[0], j4.lds_refs = l4[1], j4.lds_spheres = l4[2], j4.lds_quads = l4[3];
     j4.lds_materials = l4[4], j4.lds_textures = l4[5], j4.lds_perlin_vec = l4[6], j4.lds_perlin_perm = l4[7];
     j4.lds_stacks = l4[8];
     j4.lds_ring = l4[9];
+    j4.lds_tris = l4[10], j4.lds_tri_meta = l4[11];
     j4.trace = nullptr;  // the per-wave timeline covers the main launch's waves only
   }
   P->j4 = j4;

@@ -517,6 +517,13 @@ void prim_bbox(const rtg_primitive& p, double lo[3], double hi[3]) {
     } else {
       b = box_union(box_from_points(a0, b0), box_from_points(a1, b1));
     }
+  } else if (p.kind == RTG_PRIM_TRIANGLE) {  // the three vertices Q, Q + u, Q + v
+    double qu[3], qv[3];
+    for (int k = 0; k < 3; ++k) {
+      qu[k] = p.p0[k] + p.p1[k];
+      qv[k] = p.p0[k] + p.p2[k];
+    }
+    b = box_union(box_from_points(p.p0, qu), box_from_points(p.p0, qv));  // (thin axes padded to 0.0001 there)
   } else {
     double quv[3], qu[3], qv[3];
     for (int k = 0; k < 3; ++k) {

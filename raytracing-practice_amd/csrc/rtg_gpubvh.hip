@@ -36,7 +36,7 @@ struct Box6 {
 // The culling margin of the host builder (rtg_api.cpp culling_box; DESIGN.md §4 "conservative culling"):
 // each plane moves outward by c (|v| + M), c = 2^-21 for spheres, 2^-23 (1 + 2^-16) on an axis-aligned quad's
 // flat axis and 2^-24 (6 U + 3 |v| + 2M) on its in-plane axes (U its extent there), 2^-18 on every axis of
-// other quads; here the M terms come from the host
+// other quads and of triangles; here the M terms come from the host
 // (pads, rounded up) and the |v| terms are doubled, so that the box's own fp32 arithmetic (centre +- r, the
 // corner sums, the minimum extent, this subtraction: a few 2^-24 |v|) is covered as well
 struct CullPads {
@@ -47,10 +47,15 @@ __device__ __forceinline__ float pad_by(float v, float rel, float abs_pad) { ret
 // Box of one primitive record (the fp32 records the render kernels intersect), unpadded; thin axes other
 // than an axis-aligned quad's flat one get the reference's 0.0001 minimum extent (aabb::pad_to_minimums,
 // aabb.hpp:135-154).
-__device__ Box6 prim_box(const float4* spheres, const float4* quads, int32_t ref, int* flat) {
+// A triangle's box is its three vertices' (tri_boxes, 6 floats per slot, from the host: the plane-form record
+// the kernels intersect does not hold the vertices).
+__device__ Box6 prim_box(const float4* spheres, const float4* quads, const float* tri_boxes, int32_t ref, int* flat) {
   Box6 b;
   *flat = -1;
-  if (ref & kQuadRefBit) {
+  if (ref & kTriRefBit) {
+    const float* t = tri_boxes + static_cast<int64_t>(ref & kRefSlotMask) * 6;
+    for (int k = 0; k < 3; ++k) b.lo[k] = t[k], b.hi[k] = t[3 + k];
+  } else if (ref & kQuadRefBit) {
     const float4* q = quads + static_cast<int64_t>(ref & ~kQuadRefBit) * 5;
     const float4 Q = q[0], u = q[1], v = q[2], n = q[4];
     const float px[4] = {Q.x, Q.x + u.x, Q.x + v.x, Q.x + u.x + v.x};
@@ -99,7 +104,8 @@ __device__ __forceinline__ float o2f(uint32_t u) {
   return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
 }
 
-__global__ void prim_bounds_kernel(const float4* spheres, const float4* quads, const int32_t* refs, int64_t n,
+__global__ void prim_bounds_kernel(const float4* spheres, const float4* quads, const float* tri_boxes,
+                                   const int32_t* refs, int64_t n,
                                    CullPads pads, Box6* boxes, uint32_t* cbounds) {
   const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   float c[3] = {0.0f, 0.0f, 0.0f};
@@ -107,10 +113,11 @@ __global__ void prim_bounds_kernel(const float4* spheres, const float4* quads, c
   if (ok) {
     const int32_t ref = refs[i];
     int flat;
-    Box6 b = prim_box(spheres, quads, ref, &flat);
-    const bool quad = (ref & kQuadRefBit) != 0;
+    Box6 b = prim_box(spheres, quads, tri_boxes, ref, &flat);
+    // a triangle takes the pads of a quad that is not axis-aligned (flat < 0), as in culling_box
+    const bool quad = (ref & (kQuadRefBit | kTriRefBit)) != 0;
     float qu[3] = {0.0f, 0.0f, 0.0f}, qv[3] = {0.0f, 0.0f, 0.0f};
-    if (quad) {
+    if (ref & kQuadRefBit) {
       const float4* q = quads + static_cast<int64_t>(ref & ~kQuadRefBit) * 5;
       const float4 u = q[1], v = q[2];
       qu[0] = u.x, qu[1] = u.y, qu[2] = u.z, qv[0] = v.x, qv[1] = v.y, qv[2] = v.z;
@@ -376,7 +383,7 @@ unsigned blocks_for(int64_t n) { return static_cast<unsigned>((n + 255) / 256); 
 
 // Builds the 4-wide BVH of n primitive refs (refs_in: input order) on the device. Writes up to
 // max_nodes nodes (28 floats each) to `nodes` and the leaf-ordered refs to `refs_out` (n entries).
-hipError_t gpu_build_bvh4(const float4* spheres, const float4* quads, const int32_t* refs_in, int64_t n,
+hipError_t gpu_build_bvh4(const float4* spheres, const float4* quads, const float* tri_boxes, const int32_t* refs_in, int64_t n,
                           float m, float* nodes, int64_t max_nodes, int32_t* refs_out, GpuBvhResult* res,
                           hipStream_t st) {
   *res = GpuBvhResult{};
@@ -432,7 +439,7 @@ hipError_t gpu_build_bvh4(const float4* spheres, const float4* quads, const int3
     // rounded up by one ulp)
     const CullPads pads{m * 0x1p-21f, m * 0x1p-18f, __builtin_nextafterf(m * 0x1p-23f * (1.0f + 0x1p-16f), __builtin_inff()),
                         m * 0x1p-23f};
-    hipLaunchKernelGGL(prim_bounds_kernel, dim3(blocks_for(n)), dim3(256), 0, st, spheres, quads, refs_in, n,
+    hipLaunchKernelGGL(prim_bounds_kernel, dim3(blocks_for(n)), dim3(256), 0, st, spheres, quads, tri_boxes, refs_in, n,
                        pads, boxes, cb);
     hipLaunchKernelGGL(morton_kernel, dim3(blocks_for(n)), dim3(256), 0, st, boxes, n, cb, codes, ids);
     if ((err = rocprim::radix_sort_pairs(P(o_sort), sort_bytes, codes, codes2, ids, ids2, static_cast<size_t>(n), 0,

@@ -3,9 +3,11 @@
 //
 // Device scene layout in HBM (all 16-B aligned, read-only during a render):
 //   nodes    : float4[4*num_nodes]   64-B child-pair BVH node (both child boxes + child codes)
-//   refs     : int32[num_refs]       leaf primitive references (bit 30 = quad)
+//   refs     : int32[num_refs]       leaf primitive references (bit 30 = quad, bit 29 = triangle)
 //   spheres  : float4[2*num_spheres] {c0.xyz, r}, {dc.xyz, material}
 //   quads    : float4[5*num_quads]   {Q.xyz, D}, {u.xyz, material}, {v.xyz, -}, {w.xyz, -}, {n.xyz, -}
+//   tris     : float4[3*num_tris]    plane form, all a leaf test reads: {n.xyz, D}, {A.xyz, a0}, {B.xyz, b0}
+//   tri_meta : int2[num_tris]        {material, tie rank}: read at shading / on an exact-t tie only
 //   materials: float4[2*num_mats]    {type, texture, fuzz, eta}, {albedo.xyz, -}
 //   textures : float4[2*num_tex]     {type, even, odd, scale}, {color.xyz, image|perlin}
 //   images   : int4[num_images]      {width, height, byte offset lo, byte offset hi} + uint8 texels
@@ -23,6 +25,8 @@ namespace rtg {
 
 constexpr int32_t kEmptyChild = INT32_MIN;  // child slot with an inverted box; never visited
 constexpr int32_t kQuadRefBit = 1 << 30;
+constexpr int32_t kTriRefBit = 1 << 29;  // slot counts stay below it (compile_scene)
+constexpr int32_t kRefSlotMask = kTriRefBit - 1;
 // A perlin table's permutations as the noise lookup reads them (perlin.hpp:95-158): 16-bit lanes, each a
 // gradient index times 16 (its byte offset among the 16-B gradient rows); X[i] = (p_x[i], p_x[i+1]) in one
 // word, Y[j] = {(p_y[j], p_y[j]), (p_y[j+1], p_y[j+1])} and Z[k] = {(p_z[k], p_z[k]), (p_z[k+1], p_z[k+1])}
@@ -36,6 +40,11 @@ struct HostScene {
   std::vector<int32_t> refs;
   std::vector<float> spheres;    // 8 floats per sphere
   std::vector<float> quads;      // 20 floats per quad
+  std::vector<float> tris;       // 12 floats per triangle (the hot record)
+  std::vector<int32_t> tri_meta;  // 2 ints per triangle {material, tie rank} (the cold record)
+  // RTG_BVH_GPU only: each triangle slot's vertex box {lo.xyz, hi.xyz}, rounded outward (the plane-form
+  // records do not hold the vertices); uploaded for the device build, then dropped
+  std::vector<float> tri_boxes;
   std::vector<float> materials;  // 8 floats per material
   std::vector<float> textures;   // 8 floats per texture
   std::vector<int32_t> image_hdr;  // 4 ints per image
@@ -43,7 +52,7 @@ struct HostScene {
   std::vector<float> perlin_vec;   // 4 floats * 256 per table
   std::vector<uint32_t> perlin_perm;  // kPerlinPermWords per table
   // exact-t tie rule: the input (list-order) index of every sphere slot, then of every
-  // quad slot; read by the kernels only when a primitive's root equals the closest hit so far
+  // quad slot (a triangle's is in its cold record); read by the kernels only when a primitive's root equals the closest hit so far
   std::vector<int32_t> tie_rank;
   int64_t num_nodes = 0;
   int32_t depth = 0;
@@ -175,7 +184,8 @@ struct DevScene {
   int32_t node_width;  // 2 or 4 (see HostScene)
   int32_t num_materials;
   int32_t num_textures;
-  // leaf reference mode: 0 = look up refs[]; 1 = refs[r] == r, all spheres; 2 = refs[r] == r | quad
+  // leaf reference mode: 0 = look up refs[]; 1 = refs[r] == r, all spheres; 2 = refs[r] == r | quad;
+  // 3 = refs[r] == r | triangle
   // (single-kind scenes store primitives in reference order, so the indirection is the identity)
   int32_t ref_mode;
   int32_t tex_full;  // 1 when some texture is an image or noise texture (kernel variant selector)
@@ -200,6 +210,10 @@ struct DevScene {
   // input (reference list-order) index of each sphere slot [0, num_spheres), then of each quad slot
   // [num_spheres, num_spheres + num_quads): the exact-t tie rule of the rtg-f32 spec
   const int32_t* tie_rank;
+  // triangles (RTG_PRIM_TRIANGLE): 48-B hot records and 8-B cold records, by slot
+  const float4* tris;
+  const int2* tri_meta;
+  int64_t num_tris;
 };
 
 // A render kernel picked for a plan (rtg_kernels.hip choose_kernel); fn == nullptr: none fits.
@@ -220,7 +234,8 @@ struct GpuBvhResult {  // rtg_gpubvh.hip
   int32_t stack_need;
 };
 // m: M of the culling margin (HostScene::origin_bound, rounded up; rtg_api.cpp culling_box)
-hipError_t gpu_build_bvh4(const float4* spheres, const float4* quads, const int32_t* refs_in, int64_t n,
+// tri_boxes: 6 floats per triangle slot (HostScene::tri_boxes), null without triangles
+hipError_t gpu_build_bvh4(const float4* spheres, const float4* quads, const float* tri_boxes, const int32_t* refs_in, int64_t n,
                           float m, float* nodes, int64_t max_nodes, int32_t* refs_out, GpuBvhResult* res,
                           hipStream_t st);
 
@@ -316,6 +331,9 @@ struct DevJob {
   const int32_t* tile_order;
   // the tile-cost probe (COUNT kernels only): segments traced per tile, num_tiles counters; else null
   uint32_t* tile_cost;
+  // triangle scenes in LDS: byte offsets of the hot records and of the cold records (-1: the cold records
+  // did not fit and are read through the caches)
+  int32_t lds_tris, lds_tri_meta;
 };
 
 }  // namespace rtg

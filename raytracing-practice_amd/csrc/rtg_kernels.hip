@@ -246,10 +246,13 @@ __device__ __forceinline__ float sphere_t(float4 s0, float4 s1, V3 o, V3 d, floa
 }
 
 // Scene classes a kernel is compiled for (PRIMS): bits 0-1 the primitives its leaf test and shading
-// handle — any (the scene's ref_mode decides at run time), spheres only, quads only — and bit 2 set when
-// no material is metal or dielectric. The small-scene / dual-launch LDS kernels are built per class so
+// handle — any (the scene's ref_mode decides at run time), spheres only, quads only, triangles only — and
+// bit 2 set when no material is metal or dielectric. Bit 3 (kPrimsTriMix, with kPrimsAny): the scene holds
+// triangles beside other primitives, or triangles that the triangle-only class does not serve (cache-read
+// schedules, binary trees, 32-bit stacks): the mixed leaf test and shading carry the triangle branch. The
+// kernels without the bit are compiled exactly as before triangles existed. The small-scene / dual-launch LDS kernels are built per class so
 // a scene's kernel carries no code for what the scene lacks (default_kernel).
-constexpr int kPrimsAny = 0, kPrimsSpheres = 1, kPrimsQuads = 2, kPrimsKind = 3, kPrimsDiffuse = 4;
+constexpr int kPrimsAny = 0, kPrimsSpheres = 1, kPrimsQuads = 2, kPrimsTris = 3, kPrimsKind = 3, kPrimsDiffuse = 4, kPrimsTriMix = 8;
 
 // quad::hit (quad.hpp:44-114); plane distance D - n.O formed in f64.
 // `rank`: the quad's list index (its record's v.w, DESIGN.md §4 "tie rule"), set with a hit. `brank`: the
@@ -339,12 +342,38 @@ __device__ __forceinline__ const int32_t* tile_order_late(const DevJob& J, bool&
   return r;
 }
 // Cache-read schedules (Trav::mat holds the hit's material): the closest hit's rank is re-read from the
-// list ranks, only on a tie (wave-uniform branch).
+// list ranks (a triangle's from its cold record), only on a tie (wave-uniform branch). Quads and triangles alike.
+template <bool TRIS = false>
 __device__ __forceinline__ bool quad_wins_tie(const DevScene& S, int32_t qrank, int32_t best) {
+  if (TRIS && (best & kTriRefBit)) return qrank > S.tri_meta[best & kRefSlotMask].y;
   if (!(best & kQuadRefBit)) return true;
   return qrank > S.tie_rank[S.num_spheres + (best & ~kQuadRefBit)];
 }
 
+// Triangle (RTG_PRIM_TRIANGLE; rtg-f32 spec, DESIGN.md §4 "triangles"): the plane-form record T = {n.xyz, D},
+// {A.xyz, a0}, {B.xyz, b0}. t exactly as quad_t forms it (so a triangle coplanar with a quad gives the
+// bit-identical root), accepted in [tmin, tmax]; then the two edge-plane evaluations at p = o + t d,
+// alpha = A.p + a0 and beta = B.p + b0, each an fma chain in the x, y, z order of dot() that starts from the
+// constant. Inside: alpha >= 0, beta >= 0, alpha + beta <= 1. Returns the root or -1; ties (root == tmax)
+// are settled by the caller.
+__device__ __forceinline__ float tri_edge(float4 e, V3 p) { return fmaf(e.z, p.z, fmaf(e.y, p.y, fmaf(e.x, p.x, e.w))); }
+__device__ __forceinline__ float tri_t(const float4* T, V3 o, V3 d, float tmin, float tmax) {
+  const float4 t0 = T[0];
+  const V3 n = xyz(t0);
+  const float denom = dot(n, d);
+  if (fabsf(denom) < 1e-8f) return -1.0f;
+  const double dn = fma(static_cast<double>(n.z), static_cast<double>(o.z),
+                        fma(static_cast<double>(n.y), static_cast<double>(o.y),
+                            static_cast<double>(n.x) * static_cast<double>(o.x)));
+  const float num = static_cast<float>(static_cast<double>(t0.w) - dn);
+  const float t = div_rn(num, denom);
+  if (!(tmin <= t && t <= tmax)) return -1.0f;
+  const V3 p = madd(t, d, o);
+  const float alpha = tri_edge(T[1], p);
+  const float beta = tri_edge(T[2], p);
+  if (!(alpha >= 0.0f && beta >= 0.0f && alpha + beta <= 1.0f)) return -1.0f;
+  return t;
+}
 template <bool COUNT>
 struct Counts {
   uint32_t box = 0, prim = 0;
@@ -384,6 +413,17 @@ __device__ __forceinline__ void trav_begin(Trav& t, const DevScene& S, V3 o, V3 
   t.ix = __builtin_amdgcn_rcpf(d.x);
   t.iy = __builtin_amdgcn_rcpf(d.y);
   t.iz = __builtin_amdgcn_rcpf(d.z);
+  if constexpr (WIDE == 2) {
+    // The child-pair slab test (node_step) takes min / max of a slab's two plane distances. A direction
+    // component of exactly 0 (or a denormal) gives 1/d = inf, and plane * inf - o * inf is NaN for every plane
+    // on the origin's side of 0 but -inf for a plane below 0 (a wall at 0 padded outward): max(-inf, NaN) = -inf
+    // then culls a box the ray runs inside of, from the root down, and the ray leaves the scene. Finite
+    // reciprocals (|1/d| <= 2^100) keep both distances finite with the right signs; the test only culls, so
+    // nothing else changes. The 4-wide test picks near and far planes by the sign of 1/d and ignores the NaN.
+    t.ix = __builtin_amdgcn_fmed3f(t.ix, -0x1p100f, 0x1p100f);
+    t.iy = __builtin_amdgcn_fmed3f(t.iy, -0x1p100f, 0x1p100f);
+    t.iz = __builtin_amdgcn_fmed3f(t.iz, -0x1p100f, 0x1p100f);
+  }
   // byte offset of the far-plane rows (hi.x after lo.x, ...) in 4-wide nodes
   constexpr int32_t kHalf = 48;
   t.sx = (static_cast<uint32_t>(ibits(t.ix)) >> 31) * kHalf;
@@ -699,12 +739,36 @@ template <class Stk, bool COUNT, bool CHECK = true, bool MAT = false, int WIDE =
 __device__ __forceinline__ void leaf_step(Trav& t, const DevScene& S, V3 o, V3 d, float time,
                                           const Stk& stk, Counts<COUNT>& cnt, bool& corrupt) {
   auto pop = [&]() { trav_pop(t, stk); };
+  constexpr bool kTriMix = (PRIMS & kPrimsTriMix) != 0;  // the mixed path tests triangles too
   const int32_t code = ~t.todo;
   const int32_t first = code >> 3;
   const int32_t count = (code & 7) + 1;
   if ((CHECK || COUNT) && static_cast<int64_t>(first) + count > S.num_refs) {
     corrupt = true;
     t.todo = kTravDone;
+    return;
+  }
+  if constexpr ((PRIMS & kPrimsKind) == kPrimsTris) {
+    // triangle-only scene, records in reference order (ref = slot, no kind bit): three 16-B rows per test,
+    // nothing else; the cold record {material, rank} is read on a hit (MAT) or on an exact-t tie only
+    for (int k = 0; k < (ONE ? 1 : count); ++k) {
+      const int32_t slot = first + k;
+      if (COUNT) cnt.prim += 1;
+      // planar: a ray leaving a triangle never hits it again
+      const float th = slot == t.origin ? -1.0f : tri_t(S.tris + static_cast<int64_t>(slot) * 3, o, d, kTMin, t.tbest);
+      bool take = th > 0.0f;
+      // exact-t tie (rare; a wave-uniform branch): the triangle later in the list wins (interval::contains)
+      if (ballot_tie(th == t.tbest) != 0 && th == t.tbest) take = S.tri_meta[slot].y > S.tri_meta[t.best].y;
+      if (take) {
+        t.tbest = th;
+        t.best = slot;
+        t.mat = MAT ? S.tri_meta[slot].x : -1;
+      }
+    }
+    if (ONE && count > 1)
+      t.todo = ~(((first + 1) << 3) | (count - 2));
+    else
+      pop();
     return;
   }
   if ((PRIMS & kPrimsKind) == kPrimsSpheres || ((PRIMS & kPrimsKind) == kPrimsAny && S.ref_mode == 1)) {  // sphere-only scene, primitives stored in reference order
@@ -732,7 +796,7 @@ __device__ __forceinline__ void leaf_step(Trav& t, const DevScene& S, V3 o, V3 d
     return;
   }
   for (int k = 0; k < (ONE ? 1 : count); ++k) {
-    const int32_t ref = S.ref_mode == 0 ? S.refs[first + k] : ((first + k) | kQuadRefBit);
+    const int32_t ref = S.ref_mode == 0 ? S.refs[first + k] : ((first + k) | (kTriMix && S.ref_mode == 3 ? kTriRefBit : kQuadRefBit));
     float th;
     if (COUNT) cnt.prim += 1;
     int32_t m = 0, qrank = -1;
@@ -747,17 +811,29 @@ __device__ __forceinline__ void leaf_step(Trav& t, const DevScene& S, V3 o, V3 d
       if (MAT && th > 0.0f) m = ibits(q[1].w);
       take = th > 0.0f;
       if constexpr (MAT) {
-        if (ballot_tie(th == t.tbest) != 0 && th == t.tbest) take = quad_wins_tie(S, qrank, t.best);
+        if (ballot_tie(th == t.tbest) != 0 && th == t.tbest) take = quad_wins_tie<kTriMix>(S, qrank, t.best);
       }
+    } else if (kTriMix && (ref & kTriRefBit)) {  // planar, as a quad
+      const int32_t slot = ref & kRefSlotMask;
+      th = ref == t.origin ? -1.0f : tri_t(S.tris + static_cast<int64_t>(slot) * 3, o, d, kTMin, t.tbest);
+      take = th > 0.0f;
+      // the cold record on a hit: the material (cache-read schedules) or the list rank, which a later quad or
+      // triangle at the same t is compared with (LDS schedule: t.mat, as for a quad)
+      if (th > 0.0f) {
+        const int2 cold = S.tri_meta[slot];
+        m = cold.x;
+        qrank = cold.y;
+      }
+      if (ballot_tie(th == t.tbest) != 0 && th == t.tbest) take = MAT ? quad_wins_tie<true>(S, qrank, t.best) : qrank > t.mat;
     } else {
       const float4* sp4 = S.spheres + static_cast<int64_t>(ref) * S.sphere_f4;
       th = sphere_t<true>(sp4[0], sp4[1], o, d, t.a, t.inv_a, time, kTMin, t.tbest, ref == t.origin);
       if (MAT) m = ibits(sp4[1].w);
       take = th > 0.0f && th < t.tbest;
-      // exact-t tie: a sphere replaces only an equal-t sphere later in the list (never a quad)
+      // exact-t tie: a sphere replaces only an equal-t sphere later in the list (never a quad or triangle)
       if (ballot_tie(th == t.tbest) != 0 && th == t.tbest) {
         const int32_t* rk = tie_ranks_at_tie<COUNT>(S, corrupt);
-        take = !(t.best & kQuadRefBit) && rk[ref] < rk[t.best];
+        take = !(t.best & (kQuadRefBit | (kTriMix ? kTriRefBit : 0))) && rk[ref] < rk[t.best];
       }
     }
     if (take) {  // th > tmin >= 0.001 on a hit
@@ -953,9 +1029,19 @@ __device__ bool shade(const DevScene& S, PathState& ps, int32_t ref, float t, in
   V3 p, outward;
   float u = 0.0f, v = 0.0f;
   int mat;
+  constexpr bool kTriMix = (PRIMS & kPrimsTriMix) != 0;
   const bool sphere = (PRIMS & kPrimsKind) == kPrimsSpheres ||
-                      ((PRIMS & kPrimsKind) == kPrimsAny && !(ref & kQuadRefBit));
-  if (sphere) {
+                      ((PRIMS & kPrimsKind) == kPrimsAny && !(ref & (kQuadRefBit | (kTriMix ? kTriRefBit : 0))));
+  const bool tri = (PRIMS & kPrimsKind) == kPrimsTris || (kTriMix && (ref & kTriRefBit));
+  if (tri) {  // the plane-form record: normal, and (u, v) = (alpha, beta) of the hit point
+    const int32_t slot = ref & kRefSlotMask;
+    const float4* T = S.tris + static_cast<int64_t>(slot) * 3;
+    p = madd(t, ps.d, ps.o);
+    u = tri_edge(T[1], p);
+    v = tri_edge(T[2], p);
+    outward = xyz(T[0]);
+    mat = MAT ? mat_hit : S.tri_meta[slot].x;
+  } else if (sphere) {
     const float4* s = S.spheres + static_cast<int64_t>(ref) * S.sphere_f4;
     const float4 s0 = s[0], s1 = s[1];
     const V3 C = madd(ps.time, xyz(s1), xyz(s0));
@@ -1547,7 +1633,7 @@ __device__ __forceinline__ void render_stream(const DevScene& S, const DevCamera
 
 // Schedule 4: the same loop on a plain grid of 256-thread workgroups (scene read through the
 // caches; used when it does not fit in LDS). Waves take tiles from the same counter.
-template <int STACK, bool SPILL, bool COUNT, int WIDE, bool TEXF, bool RING>
+template <int STACK, bool SPILL, bool COUNT, int WIDE, bool TEXF, bool RING, int PRIMS = kPrimsAny>
 __global__ __launch_bounds__(256) void render_kernel(DevScene S, DevCamera C, DevJob J) {
   __shared__ int32_t s_stack[4 * STACK * 64];
   __shared__ uint32_t s_ring[RING ? 4 * kRingEntries : 1];
@@ -1561,9 +1647,9 @@ __global__ __launch_bounds__(256) void render_kernel(DevScene S, DevCamera C, De
   if constexpr (SPILL) {
     const SpillStack<STACK> stk{lstk, J.spill + static_cast<int64_t>(slot) * J.spill_depth * 64 + lane,
                                 J.lds_stack, J.lds_stack + J.spill_depth};
-    render_stream<SpillStack<STACK>, COUNT, WIDE, TEXF, kGeomGlobal, RING>(S, C, J, stk, w, rtab);
+    render_stream<SpillStack<STACK>, COUNT, WIDE, TEXF, kGeomGlobal, RING, PRIMS>(S, C, J, stk, w, rtab);
   } else {
-    render_stream<LdsStack<STACK>, COUNT, WIDE, TEXF, kGeomGlobal, RING>(S, C, J, LdsStack<STACK>{lstk}, w, rtab);
+    render_stream<LdsStack<STACK>, COUNT, WIDE, TEXF, kGeomGlobal, RING, PRIMS>(S, C, J, LdsStack<STACK>{lstk}, w, rtab);
   }
   flush_stats<COUNT>(J, w, lane_now());
   trace_wave(J, t0, w.pixels, lane_now(), slot, (blockIdx.x << 8) | wave);
@@ -1606,6 +1692,17 @@ __device__ __forceinline__ void render_lds_scene(const DevScene& S, const DevCam
   for (int64_t k = threadIdx.x; k < S.num_spheres * 2; k += kFill)
     l_spheres[(k >> 1) * J.lds_sphere_f4 + (k & 1)] = S.spheres[k];
   for (int64_t k = threadIdx.x; k < S.num_quads * 5; k += kFill) l_quads[k] = S.quads[k];
+  // triangles: the 48-B hot records as 16-B rows (three ds_read_b128 per test; the odd number of 16-B slots
+  // per record spreads a wave's reads over the banks), the 8-B cold records behind them only where they fit
+  // (J.lds_tri_meta < 0: read through the caches, on hits and ties only)
+  constexpr bool kTris = (PRIMS & kPrimsKind) == kPrimsTris || (PRIMS & kPrimsTriMix) != 0;
+  float4* l_tris = reinterpret_cast<float4*>(smem + J.lds_tris);
+  int2* l_tri_meta = reinterpret_cast<int2*>(smem + (J.lds_tri_meta < 0 ? 0 : J.lds_tri_meta));
+  if constexpr (kTris) {
+    for (int64_t k = threadIdx.x; k < S.num_tris * 3; k += kFill) l_tris[k] = S.tris[k];
+    if (J.lds_tri_meta >= 0)
+      for (int64_t k = threadIdx.x; k < S.num_tris; k += kFill) l_tri_meta[k] = S.tri_meta[k];
+  }
   if (S.ref_mode == 0)
     for (int64_t k = threadIdx.x; k < S.num_refs; k += kFill) l_refs[k] = S.refs[k];
   float4* l_pvec = reinterpret_cast<float4*>(smem + J.lds_perlin_vec);
@@ -1645,6 +1742,10 @@ __device__ __forceinline__ void render_lds_scene(const DevScene& S, const DevCam
   L.spheres = l_spheres;
   L.sphere_f4 = J.lds_sphere_f4;
   L.quads = l_quads;
+  if constexpr (kTris) {
+    L.tris = l_tris;
+    if (J.lds_tri_meta >= 0) L.tri_meta = l_tri_meta;
+  }
   L.materials = l_materials;
   L.textures = l_textures;
   if (TEXF) {
@@ -1781,16 +1882,24 @@ KernelChoice lds4_kernel(int prims, bool count, bool ring, int threads) {
       return lds_kernel<kLdsStack, false, 4, TEXF, kGeomLds, 4, kPrimsSpheres | kPrimsDiffuse>(count, ring, threads);
     case kPrimsQuads | kPrimsDiffuse:
       return lds_kernel<kLdsStack, false, 4, TEXF, kGeomLds, 4, kPrimsQuads | kPrimsDiffuse>(count, ring, threads);
+    // the triangle-only class: scenes without image / noise textures (textured ones take the mixed path)
+    case kPrimsTris:
+      if constexpr (!TEXF) return lds_kernel<kLdsStack, false, 4, false, kGeomLds, 4, kPrimsTris>(count, ring, threads);
+      return {};
+    case kPrimsTris | kPrimsDiffuse:
+      if constexpr (!TEXF)
+        return lds_kernel<kLdsStack, false, 4, false, kGeomLds, 4, kPrimsTris | kPrimsDiffuse>(count, ring, threads);
+      return {};
     default: return lds_kernel<kLdsStack, false, 4, TEXF, kGeomLds, 4, kPrimsAny>(count, ring, threads);
   }
 }
 
-template <int STACK, bool SPILL, int WIDE, bool TEXF>
+template <int STACK, bool SPILL, int WIDE, bool TEXF, int PRIMS = kPrimsAny>
 KernelChoice plain_kernel(bool count, bool ring) {
   KernelChoice k;
-  k.fn = count ? reinterpret_cast<const void*>(&render_kernel<STACK, SPILL, true, WIDE, TEXF, false>)
-         : ring ? reinterpret_cast<const void*>(&render_kernel<STACK, SPILL, false, WIDE, TEXF, true>)
-                : reinterpret_cast<const void*>(&render_kernel<STACK, SPILL, false, WIDE, TEXF, false>);
+  k.fn = count ? reinterpret_cast<const void*>(&render_kernel<STACK, SPILL, true, WIDE, TEXF, false, PRIMS>)
+         : ring ? reinterpret_cast<const void*>(&render_kernel<STACK, SPILL, false, WIDE, TEXF, true, PRIMS>)
+                : reinterpret_cast<const void*>(&render_kernel<STACK, SPILL, false, WIDE, TEXF, false, PRIMS>);
   k.block = 256;
   return k;
 }
@@ -1800,6 +1909,12 @@ KernelChoice treelet_kernel(const DevScene& S, const DevJob& J, bool count) {
   if (J.lds_stack > kLdsStack || J.stack_esz != 4 || J.lds_waves != kLdsWaves) return {};
   const bool spill = J.spill_depth > 0, tex = S.tex_full != 0, ring = J.ring_log2 >= 0 && !count;
   if (S.node_width != 4) return {};
+  // scenes with triangles: the mixed path with the triangle branch, one build (32-bit entries, the spill
+  // variant; its spill area is empty where the tree needs none)
+  constexpr int kMix = kPrimsAny | kPrimsTriMix;
+  if (S.num_tris > 0)
+    return tex ? lds_kernel<kLdsStack, true, 4, true, kGeomTreelet, kLdsWaves, kMix>(count, ring)
+               : lds_kernel<kLdsStack, true, 4, false, kGeomTreelet, kLdsWaves, kMix>(count, ring);
   // sphere-only scenes (the 1M field) get a build without the quad test (kPrimsSpheres, as default_kernel)
   const bool spheres = S.ref_mode == 1 && !tex;
   if (spill)
@@ -1818,6 +1933,20 @@ KernelChoice default_kernel(const DevScene& S, const DevJob& J, bool count, int 
   const bool spill = J.spill_depth > 0;
   const bool tex = S.tex_full != 0;
   const bool ring = J.ring_log2 >= 0 && !count;
+  // scenes with triangles outside the triangle-only class (ref_mode 3 on the 16-bit-stack LDS schedule, below):
+  // the mixed path with the triangle branch, one build per schedule, tree width and texture set (32-bit stack
+  // entries: the spill variants, whose spill area is empty where the tree needs none)
+  constexpr int kMix = kPrimsAny | kPrimsTriMix;
+  const bool tri_mix = S.num_tris > 0 && !(lds && S.ref_mode == 3 && WIDE == 4 && !spill && !tex && J.stack_esz == 2);
+  if (tri_mix && lds) {
+    if (stack != kLdsStack || J.lds_stack > kLdsStack || J.stack_esz != 4 || J.lds_waves != kLdsWaves) return {};
+    return tex ? lds_kernel<kLdsStack, true, WIDE, true, kGeomLds, kLdsWaves, kMix>(count, ring)
+               : lds_kernel<kLdsStack, true, WIDE, false, kGeomLds, kLdsWaves, kMix>(count, ring);
+  }
+  if (tri_mix) {
+    if (stack > 32 || J.lds_stack > stack) return {};
+    return tex ? plain_kernel<32, true, WIDE, true, kMix>(count, ring) : plain_kernel<32, true, WIDE, false, kMix>(count, ring);
+  }
   if (lds) {
     if (stack != kLdsStack || J.lds_stack > kLdsStack) return {};
     // 4-wide trees keep 16-bit stack entries (J.stack_esz 2) unless their leaf codes do not fit 16
@@ -1830,7 +1959,10 @@ KernelChoice default_kernel(const DevScene& S, const DevJob& J, bool count, int 
     // 4-wide trees with 16-bit stacks: the 4-wave build for both workgroup shapes (see render_kernel_lds),
     // one per primitive class (kPrimsAny...: the leaf test compiled for the scene's primitives only)
     // (a quad-only tree with a sphere occluder beside it shades spheres too: kPrimsAny)
-    const int kind = S.ref_mode == 1 ? kPrimsSpheres : (S.ref_mode == 2 && S.occluder < 0 ? kPrimsQuads : kPrimsAny);
+    // (a triangle-only tree has no occluder: only spheres become one)
+    const int kind = S.ref_mode == 1   ? kPrimsSpheres
+                     : S.ref_mode == 3 ? kPrimsTris
+                                       : (S.ref_mode == 2 && S.occluder < 0 ? kPrimsQuads : kPrimsAny);
     const int prims = kind | (S.diffuse_only ? kPrimsDiffuse : 0);
     if (WIDE == 4 && !tex && J.lds_waves == kLdsWaves)
       return lds4_kernel<false>(prims, count, ring, kLdsWaves * 64);
@@ -1906,6 +2038,8 @@ int lds_layout(const DevScene& S, int stack, int waves, int esz, DevJob* J) {
   off = a16(off + S.num_spheres * 16 * (J ? J->lds_sphere_f4 : 3));
   const int64_t quads = off;
   off = a16(off + S.num_quads * 80);
+  const int64_t tris = off;
+  off = a16(off + S.num_tris * 48);
   const int64_t refs = off;
   off = a16(off + (S.ref_mode == 0 ? S.num_refs * 4 : 0));
   const int64_t materials = off;
@@ -1916,6 +2050,13 @@ int lds_layout(const DevScene& S, int stack, int waves, int esz, DevJob* J) {
   off = a16(off + perlins * kPerlinPermWords * 4);
   const int64_t ring = off;  // RING kernels (J->ring_log2 >= 0): per-wave batch tables
   if (J && J->ring_log2 >= 0) off += int64_t(waves) * kRingEntries * 4;
+  // the triangles' cold records last, and only if they fit: beside the rest in one CU's LDS, and for the
+  // 4-wave workgroups within a fifth of it (five of them share a CU; the cold records must not cost that)
+  int64_t tri_meta = -1;
+  if (S.num_tris > 0 && off + S.num_tris * 8 <= (waves == 4 && off <= 160 * 1024 / 5 ? 160 * 1024 / 5 : 160 * 1024)) {
+    tri_meta = off;
+    off += S.num_tris * 8;
+  }
   if (off > 160 * 1024) return -1;
   if (J) {
     J->lds_materials = static_cast<int32_t>(materials);
@@ -1924,6 +2065,8 @@ int lds_layout(const DevScene& S, int stack, int waves, int esz, DevJob* J) {
     J->lds_stacks = static_cast<int32_t>(stacks);
     J->lds_spheres = static_cast<int32_t>(spheres);
     J->lds_quads = static_cast<int32_t>(quads);
+    J->lds_tris = static_cast<int32_t>(tris);
+    J->lds_tri_meta = static_cast<int32_t>(tri_meta);
     J->lds_refs = static_cast<int32_t>(refs);
     J->lds_perlin_vec = static_cast<int32_t>(pvec);
     J->lds_perlin_perm = static_cast<int32_t>(pperm);

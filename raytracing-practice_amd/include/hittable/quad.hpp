@@ -45,7 +45,7 @@ class quad : public hittable {
 
   bool rtg_flatten(rtgpu::scene_builder& sb, const vec3& offset) const override {
     rtg_primitive p{};
-    p.kind = RTG_PRIM_QUAD;
+    p.kind = rtg_kind();
     p.material = sb.material_id(mat.get());
     if (p.material < 0) return false;
     const point3 q = Q + offset;
@@ -58,13 +58,36 @@ class quad : public hittable {
     return true;
   }
 
- private:
+  // the device primitive this planar shape flattens to
+  virtual int rtg_kind() const { return RTG_PRIM_QUAD; }
+
+ protected:
   point3 Q;
   vec3 u, v, w;
   std::shared_ptr<material> mat;
   aabb bbox;
   vec3 normal;
   double D;
+};
+
+// The triangle Q, Q + u, Q + v: the quad's plane with the interior a >= 0, b >= 0, a + b <= 1 and the box of
+// its three vertices (the derived shape quad's virtual is_interior / set_bounding_box are there for).
+class triangle : public quad {
+ public:
+  triangle(const point3& Q, const vec3& u, const vec3& v, std::shared_ptr<material> mat) : quad(Q, u, v, mat) {
+    set_bounding_box();  // the base constructor ran quad's own
+  }
+
+  void set_bounding_box() override { bbox = aabb(aabb(Q, Q + u), aabb(Q, Q + v)); }
+
+  bool is_interior(double a, double b, hit_record& rec) const override {
+    if (!(a >= 0.0 && b >= 0.0 && a + b <= 1.0)) return false;
+    rec.u = a;
+    rec.v = b;
+    return true;
+  }
+
+  int rtg_kind() const override { return RTG_PRIM_TRIANGLE; }
 };
 
 // The six faces of the box spanned by opposite corners a and b.

@@ -24,7 +24,7 @@ int main(int argc, char* argv[]) {
     std::fprintf(stderr, "Error: unknown scene %s\n", name.c_str());
     return 1;
   }
-  scenes::scene s = it->second(11);
+  scenes::scene s = it->second(0);  // every scene's own default size (bouncing_spheres: grid 11)
   if (argc > 3) s.cam.image_width = std::atoi(argv[3]);
   if (argc > 4) s.cam.samples_per_pixel = std::atoi(argv[4]);
   if (argc > 5) s.cam.max_depth = std::atoi(argv[5]);

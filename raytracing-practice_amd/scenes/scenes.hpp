@@ -4,9 +4,14 @@
 // explicitly sequenced in the order GCC evaluates main.cpp (hazard H2), so the scene is the
 // reference's on every compiler.
 #pragma once
+#include <algorithm>
+#include <array>
+#include <cmath>
 #include <functional>
 #include <map>
 #include <string>
+#include <utility>
+#include <vector>
 
 #include "accelerator/bvh_node.hpp"
 #include "common/rtweekend.hpp"
@@ -262,6 +267,106 @@ inline scene tie_world(bool as_list = false) {
   return s;
 }
 
+// A parallelogram as two triangles: (Q, u, v) and (Q + u + v, -u, -v), the same plane, normal and material.
+inline void add_tri_pair(hittable_list& w, const point3& Q, const vec3& u, const vec3& v, std::shared_ptr<material> m) {
+  w.add(std::make_shared<triangle>(Q, u, v, m));
+  w.add(std::make_shared<triangle>(Q + u + v, -u, -v, m));
+}
+
+// The Cornell box of cornell_box() with every quad, the two blocks' faces included (in box()'s face order),
+// split into a triangle pair: the frame a renderer of quads gives, from a scene that holds only triangles.
+inline scene cornell_tris() {
+  auto world = std::make_shared<hittable_list>();
+  auto red = std::make_shared<lambertian>(color(0.65f, 0.05f, 0.05f));
+  auto white = std::make_shared<lambertian>(color(0.73f, 0.73f, 0.73f));
+  auto green = std::make_shared<lambertian>(color(0.12f, 0.45f, 0.15f));
+  auto light = std::make_shared<diffuse_light>(color(15.0f, 15.0f, 15.0f));
+  const double L = 555.0f;
+  hittable_list& w = *world;
+  add_tri_pair(w, point3(L, 0.0f, 0.0f), vec3(0.0f, L, 0.0f), vec3(0.0f, 0.0f, L), green);
+  add_tri_pair(w, point3(0.0f, 0.0f, 0.0f), vec3(0.0f, L, 0.0f), vec3(0.0f, 0.0f, L), red);
+  add_tri_pair(w, point3(343.0f, 554.0f, 332.0f), vec3(-130.0f, 0.0f, 0.0f), vec3(0.0f, 0.0f, -105.0f), light);
+  add_tri_pair(w, point3(0.0f, 0.0f, 0.0f), vec3(L, 0.0f, 0.0f), vec3(0.0f, 0.0f, L), white);
+  add_tri_pair(w, point3(L, L, L), vec3(-L, 0.0f, 0.0f), vec3(0.0f, 0.0f, -L), white);
+  add_tri_pair(w, point3(0.0f, 0.0f, L), vec3(L, 0.0f, 0.0f), vec3(0.0f, L, 0.0f), white);
+  auto block = [&](const point3& lo, const point3& hi) {
+    const vec3 dx(hi.x() - lo.x(), 0.0f, 0.0f), dy(0.0f, hi.y() - lo.y(), 0.0f), dz(0.0f, 0.0f, hi.z() - lo.z());
+    add_tri_pair(w, point3(lo.x(), lo.y(), hi.z()), dx, dy, white);   // front
+    add_tri_pair(w, point3(hi.x(), lo.y(), hi.z()), -dz, dy, white);  // right
+    add_tri_pair(w, point3(hi.x(), lo.y(), lo.z()), -dx, dy, white);  // back
+    add_tri_pair(w, point3(lo.x(), lo.y(), lo.z()), dz, dy, white);   // left
+    add_tri_pair(w, point3(lo.x(), hi.y(), hi.z()), dx, -dz, white);  // top
+    add_tri_pair(w, point3(lo.x(), lo.y(), lo.z()), dx, dz, white);   // bottom
+  };
+  block(point3(130.0f, 0.0f, 65.0f), point3(295.0f, 165.0f, 230.0f));
+  block(point3(265.0f, 0.0f, 295.0f), point3(430.0f, 330.0f, 460.0f));
+  scene s = cornell_box();  // its camera
+  s.world = world;
+  return s;
+}
+
+// A mesh scene generated in code: a ground triangle pair and five icosahedra subdivided `level` times onto
+// their spheres (20 * 4^level triangles each: level 1 fits the LDS schedule, level 5, the default, and above
+// render through the treelet), diffuse colours and one metal, under the sky.
+inline scene icosphere_field(int level = 5) {
+  std::vector<vec3> vtx;
+  std::vector<std::array<int, 3>> faces;
+  {
+    const double t = (1.0 + std::sqrt(5.0)) / 2.0;
+    const double v[12][3] = {{-1, t, 0}, {1, t, 0}, {-1, -t, 0}, {1, -t, 0}, {0, -1, t}, {0, 1, t},
+                             {0, -1, -t}, {0, 1, -t}, {t, 0, -1}, {t, 0, 1}, {-t, 0, -1}, {-t, 0, 1}};
+    for (const auto& p : v) vtx.push_back(unit_vector(vec3(p[0], p[1], p[2])));
+    const int f[20][3] = {{0, 11, 5}, {0, 5, 1}, {0, 1, 7}, {0, 7, 10}, {0, 10, 11}, {1, 5, 9}, {5, 11, 4},
+                          {11, 10, 2}, {10, 7, 6}, {7, 1, 8}, {3, 9, 4}, {3, 4, 2}, {3, 2, 6}, {3, 6, 8},
+                          {3, 8, 9}, {4, 9, 5}, {2, 4, 11}, {6, 2, 10}, {8, 6, 7}, {9, 8, 1}};
+    for (const auto& k : f) faces.push_back({k[0], k[1], k[2]});
+    for (int l = 0; l < level; ++l) {  // each face into four, edge midpoints pushed onto the unit sphere
+      std::map<std::pair<int, int>, int> mid;
+      auto midpoint = [&](int a, int b) {
+        const auto key = std::make_pair(std::min(a, b), std::max(a, b));
+        auto it = mid.find(key);
+        if (it != mid.end()) return it->second;
+        vtx.push_back(unit_vector(0.5 * (vtx[a] + vtx[b])));
+        return mid[key] = static_cast<int>(vtx.size()) - 1;
+      };
+      std::vector<std::array<int, 3>> next;
+      next.reserve(faces.size() * 4);
+      for (const auto& fc : faces) {
+        const int a = midpoint(fc[0], fc[1]), b = midpoint(fc[1], fc[2]), c = midpoint(fc[2], fc[0]);
+        next.push_back({fc[0], a, c});
+        next.push_back({fc[1], b, a});
+        next.push_back({fc[2], c, b});
+        next.push_back({a, b, c});
+      }
+      faces.swap(next);
+    }
+  }
+  auto world = std::make_shared<hittable_list>();
+  add_tri_pair(*world, point3(-30.0, 0.0, -30.0), vec3(0.0, 0.0, 60.0), vec3(60.0, 0.0, 0.0),
+               std::make_shared<lambertian>(color(0.5, 0.5, 0.5)));
+  const std::shared_ptr<material> mats[5] = {std::make_shared<lambertian>(color(0.7, 0.3, 0.3)),
+                                             std::make_shared<metal>(color(0.8, 0.8, 0.9), 0.05),
+                                             std::make_shared<lambertian>(color(0.3, 0.6, 0.3)),
+                                             std::make_shared<lambertian>(color(0.3, 0.4, 0.8)),
+                                             std::make_shared<lambertian>(color(0.8, 0.7, 0.2))};
+  const double place[5][4] = {{0.0, 1.5, 0.0, 1.5}, {-3.5, 1.0, 1.0, 1.0}, {3.5, 1.0, 1.0, 1.0},
+                              {-1.8, 0.6, 3.2, 0.6}, {1.8, 0.6, 3.2, 0.6}};  // centre, radius
+  for (int k = 0; k < 5; ++k) {
+    const point3 c(place[k][0], place[k][1], place[k][2]);
+    for (const auto& fc : faces) {
+      const point3 q = c + place[k][3] * vtx[fc[0]];
+      world->add(std::make_shared<triangle>(q, c + place[k][3] * vtx[fc[1]] - q, c + place[k][3] * vtx[fc[2]] - q, mats[k]));
+    }
+  }
+  scene s{world, camera()};
+  s.cam.image_width = 1920;
+  s.cam.aspect_ratio = 16.0 / 9.0;
+  s.cam.samples_per_pixel = 64;
+  s.cam.max_depth = 50;
+  sky_camera(s.cam, 30.0, point3(0.0, 4.0, 14.0), point3(0.0, 1.0, 0.0), color(0.7, 0.8, 1.0));
+  return s;
+}
+
 inline const std::map<std::string, std::function<scene(int)>>& registry() {
   static const std::map<std::string, std::function<scene(int)>> r = {
       {"bouncing_spheres", [](int g) { return bouncing_spheres(g > 0 ? g : 11); }},
@@ -274,6 +379,8 @@ inline const std::map<std::string, std::function<scene(int)>>& registry() {
       {"cornell_translate", [](int) { return cornell_translate(); }},
       {"earth_perlin", [](int) { return earth_perlin(); }},
       {"tie_world", [](int g) { return tie_world(g == 1); }},  // grid 1: the plain list
+      {"cornell_tris", [](int) { return cornell_tris(); }},
+      {"icosphere_field", [](int g) { return icosphere_field(g > 0 ? g : 5); }},  // grid: subdivision level
   };
   return r;
 }
