@@ -367,6 +367,66 @@ rtg_status rtg_hot_treelet_order_host(int32_t* nodes, const uint32_t* visits, in
 rtg_status rtg_resolve_rgb8(rtg_scene* scene, const float* in_rgb, uint8_t* out_rgb8,
                             int64_t n_pixels, void* stream);
 
+/* ---- batched ray queries (additive in ABI 7; no reference counterpart: hittable::hit for N rays of the
+ * caller's own) ----
+ * rtg_intersect answers `num_rays` rays against the scene: the closest hit of each, or (RTG_QUERY_ANY)
+ * whether anything is hit at all. Traversal only: no camera, no materials, no shading.
+ *  - Interval: a sphere root counts in (tmin, tmax), a quad or triangle root in [tmin, tmax] (the reference's
+ *    interval::surrounds / contains split, as in the render). A tmin below 2^-126 counts as 2^-126: a root at
+ *    t <= 0 is never a hit. tmax may be +inf.
+ *  - The primitive tests and the exact-t tie rule are the render's; there is no origin primitive. With
+ *    tmin = 0.001f and tmax = inf a closest-hit query returns exactly the t and the winner of a render segment
+ *    with that origin, direction and time. The sphere kept out of the BVH (book-1's ground) is tested by every ray.
+ *  - rtg_hit: `prim` is the index into rtg_scene_desc.prims, -1 on a miss (then t = -1 and the rest is 0);
+ *    (u, v) are get_sphere_uv's on a sphere, (alpha, beta) on a quad or triangle; `normal` is the unit
+ *    geometric normal turned against the ray and `front_face` as in hit_record (set_face_normal).
+ *  - RTG_QUERY_ANY: prim >= 0 iff some primitive has a root in the interval; the record is that of a primitive
+ *    that really has that root, not necessarily the nearest.
+ *  - num_rays == 0 is RTG_OK and launches nothing; a ray with a non-finite component (or a NaN tmin / tmax /
+ *    time), an origin coordinate of 1e30 or more in magnitude, or dir == 0 is a miss for that ray, not an error.
+ *    num_rays >= 2^31 is RTG_E_UNSUPPORTED.
+ *  - Validation order: the descriptor (NULL, negative num_rays, ASYNC without DEVICE, unknown flags, NULL
+ *    arrays) is checked before the scene is looked at, and all of it before any device work.
+ *  - Host pointers are staged through grow-only pinned and device buffers of the scene: steady-state queries
+ *    allocate nothing. With RTG_QUERY_DEVICE the call first reads back the batch's largest |origin| (the
+ *    culling margin depends on it), so it waits for the stream's earlier work once; with RTG_QUERY_ASYNC it
+ *    then returns once the query is enqueued, `stats` holds only `rays`, and traversal errors are reported by
+ *    the scene's next rtg_intersect. Not concurrent with renders of the same scene; rtg_render, rtg_scene_prepare
+ *    and rtg_intersect wait for a query still in flight before they use the scene's scratch. */
+typedef struct rtg_ray {
+  float origin[3];
+  float tmin;
+  float dir[3];
+  float tmax;
+} rtg_ray; /* 32 B */
+typedef struct rtg_hit {
+  float t;
+  int32_t prim;
+  float u, v;
+  float normal[3];
+  int32_t front_face;
+} rtg_hit; /* 32 B */
+#define RTG_QUERY_ANY 0x1    /* occlusion query: traversal ends at the first accepted hit */
+#define RTG_QUERY_DEVICE 0x2 /* rays / times / hits are device pointers on the scene's device */
+#define RTG_QUERY_ASYNC 0x4  /* needs DEVICE; returns once enqueued on `stream` */
+/* bits 8-15: RTG_RENDER_SCHEDULE(n), the same diagnostic selector as rtg_render: 0 default, 3 scene in LDS,
+ * 4 plain grid through the caches, 5 treelet; a schedule the scene cannot run is RTG_E_UNSUPPORTED */
+typedef struct rtg_query_desc {
+  const rtg_ray* rays;
+  const float* times; /* one per ray, or NULL: 0 for every ray */
+  int64_t num_rays;
+  rtg_hit* hits;
+  int32_t flags;
+  int32_t max_workgroups; /* 0: library default */
+  void* stream;           /* hipStream_t, NULL: the scene's own stream */
+} rtg_query_desc;
+typedef struct rtg_query_stats {
+  uint64_t rays, hits;
+  double kernel_ms;
+  uint64_t reserved_[5]; /* [0] schedule run, [1] workgroups, [2] waves per workgroup, [3] LDS bytes per workgroup */
+} rtg_query_stats;
+rtg_status rtg_intersect(rtg_scene* scene, const rtg_query_desc* q, rtg_query_stats* stats);
+
 /* ---- multi-GPU frames: row-interleaved shards, one RCCL gather over xGMI ----
  * Replaces the reference's single-device pixel loop of camera::render (camera.hpp:29-72) when the
  * image is tiled over several GPUs: rank r renders rows r, r+N, r+2N, ... (any N gives the same

@@ -32,6 +32,13 @@ int lds_layout(const DevScene& S, int stack, int waves, int esz, DevJob* J);
 int lds_layout_treelet(DevScene* S, int stack, int waves, DevJob* J);
 bool dual_fits_registers(bool count, bool ring, bool verbose);
 hipError_t launch_resolve(const float* in, uint8_t* out, int64_t n_pixels, hipStream_t stream);
+// ray queries (rtg_query.hip)
+KernelChoice choose_query_kernel(const DevScene& S, int variant, bool any, bool spill);
+int query_lds_layout(const DevScene& S, int waves, int entries, DevQuery* Q);
+int query_treelet_layout(DevScene* S, int waves, int entries, DevQuery* Q);
+hipError_t launch_query(const KernelChoice& k, const DevScene& S, const DevQuery& Q, int lds_bytes, int grid_blocks,
+                        hipStream_t stream);
+hipError_t launch_origin_reach(const void* rays, uint32_t n, unsigned int* out, hipStream_t stream);
 }  // namespace rtg
 
 using namespace rtg;
@@ -56,7 +63,8 @@ constexpr int kSmallSceneWgs = 5;       // 4-wave persistent workgroups per CU f
 // bookkeeping and its HBM writes drop from 16.3 GB (ring slots + the ring kernel's scratch) to the
 // partials' 6.3 GB (profiles/r05_dd, r05_final); the ring remains for frames whose partials would not fit
 constexpr int64_t kRingAutoBytes = int64_t(32) << 30;
-constexpr int kNumCounters = 28;        // see DevJob::counters ([8..23] diagnostics, [24..25] tile ring, [26] stack spills)
+constexpr int kNumCounters = 28;        // see DevJob::counters ([8..23] diagnostics, [24..25] tile ring, [26] stack spills,
+                                        // [27] a device query batch's origin reach, float bits: rtg_intersect)
 // gfx950 allocates a workgroup's LDS in 1280-byte granules (160 KB = 128 of them): measured with the
 // dual launch, whose two workgroups stop sharing a CU exactly when the rounded sizes pass 160 KB
 constexpr int kLdsGranule = 1280;
@@ -334,6 +342,7 @@ Knobs read_knobs() {
   num("RTG_TREELET_HOT", 0, 1, &k.treelet_hot);
   num("RTG_TILE_ORDER", 0, 1, &k.tile_order);
   num("RTG_TILE_ORDER_SPP", 1, 64, &k.tile_order_spp);
+  num("RTG_QUERY_REFILL", 1, 64, &k.query_refill);
   if (const char* e = std::getenv("RTG_WAVE_TRACE")) k.wave_trace = e;
   return k;
 }
@@ -722,6 +731,16 @@ bool compile_scene(const rtg_scene_desc* d, HostScene* out, std::string* err) {
   for (int64_t i = 0; i < d->num_prims; ++i)
     if (slot[i] >= 0 && d->prims[i].kind != RTG_PRIM_TRIANGLE)
       out->tie_rank[(d->prims[i].kind == RTG_PRIM_QUAD ? nsph : 0) + slot[i]] = static_cast<int32_t>(tie_rank(i));
+  // ray queries report input indices: the slot table (spheres, quads, triangles)
+  if (d->num_prims < (int64_t(1) << 31)) {
+    out->prim_index.assign(static_cast<size_t>(nsph) + nquad + ntri, -1);
+    for (int64_t i = 0; i < d->num_prims; ++i)
+      if (slot[i] >= 0) {
+        const int kind = d->prims[i].kind;
+        const int64_t base = kind == RTG_PRIM_QUAD ? nsph : (kind == RTG_PRIM_TRIANGLE ? int64_t(nsph) + nquad : 0);
+        out->prim_index[base + slot[i]] = static_cast<int32_t>(i);
+      }
+  }
   phase("prims");
   // culling boxes (the margin above) in place of the reference's, then rounded outward
   if (out->node_width == 4) refit_culling_boxes<BuildNode4, 4>(bvh4.nodes, bvh.refs, d, out->origin_bound);
@@ -973,6 +992,14 @@ struct rtg_scene {
   int64_t order_tiles = 0, order_cap = 0;
   double order_tune_ms = 0.0;
   uint32_t* probe_tile_cost = nullptr;  // set only while the tile-cost probe runs
+  // ray queries (rtg_intersect): the slot-to-input-index table (host copy from scene creation; uploaded by the
+  // first query, so scenes that never query keep their device bytes and allocation counts), the staging of
+  // host-pointer batches (device: rays, hits, times; pinned host: host_stage) and an async query in flight
+  std::vector<int32_t> prim_index;
+  int32_t* prim_index_dev = nullptr;
+  ScratchBuf scr_query;
+  bool query_pending = false;
+  hipStream_t query_stream = nullptr;
   // deferred (async) render state
   bool pending = false;
   hipStream_t pending_stream = nullptr;
@@ -1266,6 +1293,7 @@ rtg_status rtg_scene_create(const rtg_scene_desc* desc_in, int32_t device, rtg_s
                          reinterpret_cast<const int32_t*>(hs.nodes.data()) + hs.nodes.size());
 
   s->origin_bound = hs.origin_bound;
+  s->prim_index = std::move(hs.prim_index);
   s->info.device = device;
   s->info.bvh_mode = desc->bvh_mode;
   s->info.num_prims = hs.num_prims;
@@ -1300,7 +1328,9 @@ void rtg_scene_destroy(rtg_scene* s) {
   if (s->host_stage) (void)hipHostFree(s->host_stage);
   if (s->dev_out) (void)hipFree(s->dev_out);
   if (s->order_dev) (void)hipFree(s->order_dev);
-  for (ScratchBuf* b : {&s->scr_spill, &s->scr_trace, &s->scr_partial})
+  if (s->query_pending && s->query_stream) (void)hipStreamSynchronize(s->query_stream);
+  if (s->prim_index_dev) (void)hipFree(s->prim_index_dev);
+  for (ScratchBuf* b : {&s->scr_spill, &s->scr_trace, &s->scr_partial, &s->scr_query})
     if (b->p) (void)hipFree(b->p);
   if (s->ev0) (void)hipEventDestroy(s->ev0);
   if (s->ev1) (void)hipEventDestroy(s->ev1);
@@ -1860,15 +1890,11 @@ rtg_status tune_tile_order(rtg_scene* s, const rtg_camera_desc* cam, const rtg_r
 // node box on the device first (repad_nodes_kernel, on the render's stream; 1/16 headroom so a camera moving
 // about does not repad every frame) by 2^-20 per unit of M added: the most any margin's origin terms grow (a
 // quad's in-plane axes, 7 2^-24 |o|). Boxes only grow: frames are unchanged, the bound holds again.
-rtg_status ensure_origin_bound(rtg_scene* s, const rtg_camera_desc* cam, hipStream_t stream) {
+// mc: the largest |coordinate| of the ray origins to cover (a camera's lens, a query's rays)
+rtg_status ensure_origin_reach(rtg_scene* s, double mc, hipStream_t stream) {
   if (s->dev.num_nodes <= 0) return RTG_OK;
-  rtg_camera_params cp;
-  resolve_camera(cam, &cp);
-  double mc = 0.0;
-  for (int a = 0; a < 3; ++a)
-    mc = std::max(mc, std::fabs(cp.center[a]) + std::fabs(cp.defocus_disk_u[a]) + std::fabs(cp.defocus_disk_v[a]));
   if (mc <= 2.0 * s->origin_bound) return RTG_OK;
-  if (!(mc < 1e30)) return fail(RTG_E_INVALID, "camera position not finite (or above 1e30)");
+  if (!(mc < 1e30)) return fail(RTG_E_INVALID, "ray origins (camera position) not finite (or above 1e30)");
   const double target = 0.5 * mc * (1.0 + 1.0 / 16.0);
   const float delta = round_up(0x1p-20 * (target - s->origin_bound));
   RTG_HIP(launch_repad(reinterpret_cast<float*>(const_cast<float4*>(s->dev.nodes)), s->dev.num_nodes,
@@ -1880,6 +1906,26 @@ rtg_status ensure_origin_bound(rtg_scene* s, const rtg_camera_desc* cam, hipStre
   s->origin_bound = target;
   s->host_nodes.clear();  // the hot treelet downloads the repadded array when it next tunes
   if (s->knobs.verbose) std::fprintf(stderr, "[rtg] culling margin widened for origins up to %.6g\n", target);
+  return RTG_OK;
+}
+rtg_status ensure_origin_bound(rtg_scene* s, const rtg_camera_desc* cam, hipStream_t stream) {
+  if (s->dev.num_nodes <= 0) return RTG_OK;
+  rtg_camera_params cp;
+  resolve_camera(cam, &cp);
+  double mc = 0.0;
+  for (int a = 0; a < 3; ++a)
+    mc = std::max(mc, std::fabs(cp.center[a]) + std::fabs(cp.defocus_disk_u[a]) + std::fabs(cp.defocus_disk_v[a]));
+  return ensure_origin_reach(s, mc, stream);
+}
+
+// An async query still in flight: wait for it and report what its traversal met (rtg_intersect).
+rtg_status finish_query(rtg_scene* s) {
+  if (!s->query_pending) return RTG_OK;
+  s->query_pending = false;
+  RTG_HIP(hipStreamSynchronize(s->query_stream), "query stream");
+  const unsigned long long* c = s->host_counters;
+  if (c[4] != 0) return fail(RTG_E_UNSUPPORTED, "BVH traversal stack overflow in " + std::to_string(c[4]) + " waves (query)");
+  if (c[5] != 0) return fail(RTG_E_INVALID, "corrupt BVH child code met during a query's traversal");
   return RTG_OK;
 }
 
@@ -1942,6 +1988,10 @@ rtg_status rtg_render_plan(rtg_scene* s, const rtg_camera_desc* cam, const rtg_r
 rtg_status rtg_scene_prepare(rtg_scene* s, const rtg_camera_desc* cam, const rtg_render_desc* job) {
   if (!s || !cam || !job) return fail(RTG_E_INVALID, "null argument");
   if (s->pending) return fail(RTG_E_INVALID, "a previous async render was not waited for");
+  if (s->query_pending) {  // its probes use the counters and spill area an async query may still hold
+    RTG_HIP(hipSetDevice(s->device), "hipSetDevice");
+    (void)finish_query(s);
+  }
   Plan P;
   rtg_status pst = plan_render(s, cam, job, &P);
   if (pst != RTG_OK) return pst;
@@ -1977,6 +2027,10 @@ rtg_status rtg_render(rtg_scene* s, const rtg_camera_desc* cam, const rtg_render
   if (!s || !cam || !job) return fail(RTG_E_INVALID, "null argument");
   if (!out_rgb && !job->partial) return fail(RTG_E_INVALID, "null output buffer");
   if (s->pending) return fail(RTG_E_INVALID, "a previous async render was not waited for");
+  if (s->query_pending) {  // an async query still uses the scene's counters and spill area
+    RTG_HIP(hipSetDevice(s->device), "hipSetDevice");
+    (void)finish_query(s);  // its errors belong to the query, not to this render
+  }
   Plan P;
   rtg_status pst = plan_render(s, cam, job, &P);
   if (pst != RTG_OK) return pst;
@@ -2154,6 +2208,207 @@ rtg_status rtg_resolve_rgb8(rtg_scene* s, const float* in_rgb, uint8_t* out_rgb8
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : s->own_stream;
   RTG_HIP(launch_resolve(in_rgb, out_rgb8, n_pixels, st), "resolve kernel launch");
   if (!stream) RTG_HIP(hipStreamSynchronize(st), "resolve kernel");
+  return RTG_OK;
+}
+
+rtg_status rtg_intersect(rtg_scene* s, const rtg_query_desc* q, rtg_query_stats* stats) {
+  // the descriptor first, then the scene (rtgpu.h): nothing of the scene is read before these checks
+  if (!q) return fail(RTG_E_INVALID, "null query descriptor");
+  if (stats) *stats = rtg_query_stats{};
+  if (q->num_rays < 0) return fail(RTG_E_INVALID, "num_rays is negative");
+  const bool any = (q->flags & RTG_QUERY_ANY) != 0, dev = (q->flags & RTG_QUERY_DEVICE) != 0;
+  const bool async = (q->flags & RTG_QUERY_ASYNC) != 0;
+  if (async && !dev) return fail(RTG_E_INVALID, "RTG_QUERY_ASYNC requires RTG_QUERY_DEVICE");
+  if (q->flags & ~(RTG_QUERY_ANY | RTG_QUERY_DEVICE | RTG_QUERY_ASYNC | 0xff00))
+    return fail(RTG_E_INVALID, "unknown query flags");
+  if (q->max_workgroups < 0) return fail(RTG_E_INVALID, "max_workgroups is negative");
+  if (q->num_rays > 0 && (!q->rays || !q->hits)) return fail(RTG_E_INVALID, "null ray or hit array");
+  if (q->num_rays >= (int64_t(1) << 31)) return fail(RTG_E_UNSUPPORTED, "num_rays must be below 2^31 (split the batch)");
+  if (!s) return fail(RTG_E_INVALID, "null scene");
+  if (s->pending) return fail(RTG_E_INVALID, "a previous async render was not waited for");
+  int variant = (q->flags >> 8) & 0xff;
+  if (variant != 0 && variant != 3 && variant != 4 && variant != 5) return fail(RTG_E_INVALID, "unknown query schedule");
+  RTG_HIP(hipSetDevice(s->device), "hipSetDevice");
+  rtg_status st = finish_query(s);
+  if (st != RTG_OK) return st;
+  if (s->prim_index.empty() && s->dev.num_refs + (s->dev.occluder >= 0 ? 1 : 0) > 0)
+    return fail(RTG_E_UNSUPPORTED, "ray queries need fewer than 2^31 primitives");
+
+  // ---- the launch plan: the schedule from the query's own LDS need (no materials, textures or noise tables)
+  const Knobs& K = s->knobs;
+  const int need = std::max(1, s->stack_need);
+  int entries = K.stack_lds_entries > 0 ? std::min(kLdsStack, K.stack_lds_entries) : kLdsStack;
+  const bool spill = need > entries;
+  if (!spill) entries = kLdsStack;  // the LdsStack kernels' layout
+  DevScene dscene = s->dev;
+  dscene.node_visits = nullptr;
+  DevQuery dq{};
+  // resident waves per SIMD the compiled kernel allows (512 registers per lane, granule 8)
+  auto waves_per_simd = [](const KernelChoice& k) {
+    const KernelResources r = kernel_resources(k.fn);
+    return r.ok && r.vgprs > 0 ? std::max(1, std::min(8, 512 / ((r.vgprs + 7) / 8 * 8))) : 4;
+  };
+  KernelChoice kc;
+  int lds_bytes = 0, wgs_per_cu = 1, waves = 4;
+  if (variant == 0 || variant == 3) {
+    kc = choose_query_kernel(dscene, 3, any, spill);
+    int best = 0;
+    if (kc.fn) {
+      const int wps = waves_per_simd(kc);
+      for (const int w : {16, 8, 4}) {  // the shape with the most resident waves; ties to the larger workgroup
+        const int b = query_lds_layout(dscene, w, entries, nullptr);
+        if (b < 0) continue;
+        const int g = std::min(kLdsPerCu / lds_alloc(b), wps * 4 / w);
+        if (g * w > best) best = g * w, waves = w, wgs_per_cu = g;
+      }
+    }
+    if (best > 0) {
+      variant = 3;
+      lds_bytes = query_lds_layout(dscene, waves, entries, &dq);
+    } else if (variant == 3) {
+      return fail(RTG_E_UNSUPPORTED, "scene does not fit the LDS query schedule (or its tree is not 4-wide)");
+    } else {
+      variant = dscene.node_width == 4 ? 5 : 4;
+    }
+  }
+  if (variant == 5) {
+    kc = choose_query_kernel(dscene, 5, any, spill);
+    if (!kc.fn) return fail(RTG_E_UNSUPPORTED, "the treelet query schedule needs a 4-wide BVH");
+    waves = kLdsWaves;
+    wgs_per_cu = 1;
+    lds_bytes = query_treelet_layout(&dscene, waves, entries, &dq);
+    if (lds_bytes < 0) return fail(RTG_E_UNSUPPORTED, "no LDS room for the treelet");
+  } else if (variant == 4) {
+    kc = choose_query_kernel(dscene, 4, any, spill);
+    waves = 4;
+    // 16 KiB of static LDS stacks per workgroup
+    wgs_per_cu = std::max(1, std::min(waves_per_simd(kc), kLdsPerCu / lds_alloc(4 * kLdsStack * 64 * 4)));
+  }
+  if (!kc.fn) return fail(RTG_E_UNSUPPORTED, "no query kernel fits this scene");
+  kc.block = waves * 64;
+  if (stats) {
+    stats->reserved_[0] = static_cast<uint64_t>(variant);
+    stats->reserved_[2] = static_cast<uint64_t>(waves);
+    stats->reserved_[3] = static_cast<uint64_t>(kc.dynamic_lds ? lds_bytes : 4 * kLdsStack * 64 * 4);
+  }
+  if (q->num_rays == 0) return RTG_OK;  // nothing to launch
+  const int64_t n = q->num_rays;
+  int64_t grid = int64_t(s->num_cus) * wgs_per_cu;
+  if (q->max_workgroups > 0) grid = std::min<int64_t>(grid, q->max_workgroups);
+  grid = std::max<int64_t>(1, std::min(grid, (n + kc.block - 1) / kc.block));  // what the rays can fill
+  if (stats) stats->reserved_[1] = static_cast<uint64_t>(grid);
+  dq.num_rays = static_cast<uint32_t>(n);
+  dq.lds_stack = entries;
+  dq.spill_depth = std::max(0, need - entries);
+  dq.refill_batch = K.query_refill;
+  // rays a wave reserves per cursor add: an eighth of a wave's share of the batch (so the launch's tail stays
+  // short), within 64..512
+  dq.block = static_cast<int32_t>(std::max<int64_t>(64, std::min<int64_t>(512, n / (grid * waves * 8) / 64 * 64)));
+  dq.leaf_batch = s->dev.num_nodes <= kSmallBvhNodes ? kSmallBvhLeafBatch : kDefaultLeafBatch;  // as the render
+
+  hipStream_t stream = q->stream ? static_cast<hipStream_t>(q->stream) : s->own_stream;
+  SyncOnError sync_on_error;
+  sync_on_error.stream = stream;
+  auto grow = [](ScratchBuf& b, size_t bytes, const char* what) -> rtg_status {
+    if (b.p && b.bytes >= bytes) return RTG_OK;
+    if (b.p) RTG_HIP(hipFree(b.p), "hipFree(scratch)");  // device-synchronous: nothing still reads it
+    b.p = nullptr;
+    b.bytes = 0;
+    RTG_HIP(dev_alloc(&b.p, std::max<size_t>(bytes, 256)), what);
+    b.bytes = bytes;
+    return RTG_OK;
+  };
+  if (!s->prim_index_dev && !s->prim_index.empty()) {  // the scene's first query
+    RTG_HIP(dev_alloc(reinterpret_cast<void**>(&s->prim_index_dev), s->prim_index.size() * 4), "hipMalloc(prim index)");
+    RTG_HIP(hipMemcpy(s->prim_index_dev, s->prim_index.data(), s->prim_index.size() * 4, hipMemcpyHostToDevice),
+            "hipMemcpy(prim index)");
+  }
+  dq.prim_index = s->prim_index_dev;
+  dq.counters = s->counters;
+  RTG_HIP(hipMemsetAsync(s->counters, 0, kNumCounters * sizeof(unsigned long long), stream), "hipMemsetAsync");
+  double reach = 0.0;  // the largest |origin coordinate| (below 1e30) of the batch
+  const size_t ray_bytes = static_cast<size_t>(n) * sizeof(rtg_ray), time_bytes = q->times ? static_cast<size_t>(n) * 4 : 0;
+  if (dev) {
+    dq.rays = reinterpret_cast<const float4*>(q->rays);
+    dq.times = q->times;
+    dq.hits = reinterpret_cast<float4*>(q->hits);
+    unsigned int* word = reinterpret_cast<unsigned int*>(s->counters + 27);
+    RTG_HIP(launch_origin_reach(q->rays, dq.num_rays, word, stream), "origin reach kernel launch");
+    RTG_HIP(hipMemcpyAsync(s->host_counters + 27, s->counters + 27, 8, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(reach)");
+    RTG_HIP(hipStreamSynchronize(stream), "origin reach kernel");
+    float f;
+    const uint32_t bits = static_cast<uint32_t>(s->host_counters[27]);
+    std::memcpy(&f, &bits, 4);
+    reach = f;
+  } else {
+    // pinned staging (the scene's host_stage), then one DMA each way; rays | hits | times on the device
+    const size_t stage_bytes = ray_bytes + time_bytes;  // >= the hits' bytes
+    if (s->host_stage_bytes < stage_bytes) {
+      if (s->host_stage) RTG_HIP(hipHostFree(s->host_stage), "hipHostFree(stage)");
+      s->host_stage = nullptr;
+      s->host_stage_bytes = 0;
+      RTG_HIP(host_alloc(&s->host_stage, stage_bytes), "hipHostMalloc(stage)");
+      s->host_stage_bytes = stage_bytes;
+    }
+    st = grow(s->scr_query, 2 * ray_bytes + static_cast<size_t>(n) * 4, "hipMalloc(query staging)");
+    if (st != RTG_OK) return st;
+    char* stage = static_cast<char*>(s->host_stage);
+    std::memcpy(stage, q->rays, ray_bytes);
+    if (q->times) std::memcpy(stage + ray_bytes, q->times, time_bytes);
+    float m = 0.0f;
+    for (int64_t k = 0; k < n; ++k)
+      for (int a = 0; a < 3; ++a) {
+        const float v = std::fabs(q->rays[k].origin[a]);
+        if (v < 1e30f && v > m) m = v;  // (a ray from farther out is a miss: rtg_query.hip kQueryOriginLimit)
+      }
+    reach = m;
+    char* dbase = static_cast<char*>(s->scr_query.p);
+    RTG_HIP(hipMemcpyAsync(dbase, stage, ray_bytes, hipMemcpyHostToDevice, stream), "hipMemcpy(rays)");
+    if (q->times)
+      RTG_HIP(hipMemcpyAsync(dbase + 2 * ray_bytes, stage + ray_bytes, time_bytes, hipMemcpyHostToDevice, stream),
+              "hipMemcpy(times)");
+    dq.rays = reinterpret_cast<const float4*>(dbase);
+    dq.hits = reinterpret_cast<float4*>(dbase + ray_bytes);
+    dq.times = q->times ? reinterpret_cast<const float*>(dbase + 2 * ray_bytes) : nullptr;
+  }
+  st = ensure_origin_reach(s, reach, stream);
+  if (st != RTG_OK) return st;
+  dq.spill = nullptr;
+  if (dq.spill_depth > 0) {  // the render's spill area (queries and renders of a scene never overlap)
+    st = grow(s->scr_spill, static_cast<size_t>(grid) * waves * 64 * dq.spill_depth * sizeof(int32_t), "hipMalloc(stack spill)");
+    if (st != RTG_OK) return st;
+    dq.spill = static_cast<int32_t*>(s->scr_spill.p);
+  }
+  if (K.verbose)
+    std::fprintf(stderr, "[rtg] query schedule %d (%s): %lld workgroups of %d waves (%d per CU), %d B LDS, stack %d + %d\n",
+                 variant, any ? "any" : "closest", static_cast<long long>(grid), waves, wgs_per_cu, lds_bytes,
+                 dq.lds_stack, dq.spill_depth);
+  RTG_HIP(hipEventRecord(s->ev0, stream), "hipEventRecord");
+  RTG_HIP(launch_query(kc, dscene, dq, lds_bytes, static_cast<int>(grid), stream), "query kernel launch");
+  RTG_HIP(hipEventRecord(s->ev1, stream), "hipEventRecord");
+  RTG_HIP(hipMemcpyAsync(s->host_counters, s->counters, kNumCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                         stream),
+          "hipMemcpyAsync(counters)");
+  if (!dev) RTG_HIP(hipMemcpyAsync(s->host_stage, dq.hits, ray_bytes, hipMemcpyDeviceToHost, stream), "hipMemcpy(hits)");
+  sync_on_error.committed = true;
+  s->query_pending = true;
+  s->query_stream = stream;
+  if (async) {
+    if (stats) stats->rays = static_cast<uint64_t>(n);
+    return RTG_OK;
+  }
+  st = finish_query(s);
+  float ms = 0.0f;
+  RTG_HIP(hipEventElapsedTime(&ms, s->ev0, s->ev1), "hipEventElapsedTime");
+  if (stats) {
+    stats->rays = s->host_counters[0];
+    stats->hits = s->host_counters[3];
+    stats->kernel_ms = ms;
+  }
+  if (st != RTG_OK) return st;
+  if (s->host_counters[0] != static_cast<unsigned long long>(n))
+    return fail(RTG_E_HIP, "the query answered " + std::to_string(s->host_counters[0]) + " of " + std::to_string(n) + " rays");
+  if (!dev) std::memcpy(q->hits, s->host_stage, ray_bytes);
   return RTG_OK;
 }
 

@@ -54,6 +54,9 @@ struct HostScene {
   // exact-t tie rule: the input (list-order) index of every sphere slot, then of every
   // quad slot (a triangle's is in its cold record); read by the kernels only when a primitive's root equals the closest hit so far
   std::vector<int32_t> tie_rank;
+  // ray queries (rtg_intersect): the input index (into rtg_scene_desc.prims) of every sphere slot, then of every
+  // quad slot, then of every triangle slot; uploaded on the scene's first query
+  std::vector<int32_t> prim_index;
   int64_t num_nodes = 0;
   int32_t depth = 0;
   int32_t stack_need = 0;  // traversal stack entries needed (<= depth for BVH2)
@@ -277,6 +280,8 @@ struct Knobs {
   int tile_order = 1;           // RTG_TILE_ORDER 0 | 1: rtg_scene_prepare orders the tile hand-out by a
                                 // probe render's per-tile cost (1), or leaves it tile-major (0)
   int tile_order_spp = 4;       // RTG_TILE_ORDER_SPP 1..64: samples per pixel of that probe (at most the render's)
+  int query_refill = 48;        // RTG_QUERY_REFILL 1..64: of 64 live lanes, the finished ones that start a query
+                                // wave's write-out and refill pass (DESIGN.md §3 "ray queries")
   std::string wave_trace;      // RTG_WAVE_TRACE=<file>: per-wave timeline (tools/wave_trace.py)
 };
 Knobs read_knobs();
@@ -334,6 +339,26 @@ struct DevJob {
   // triangle scenes in LDS: byte offsets of the hot records and of the cold records (-1: the cold records
   // did not fit and are read through the caches)
   int32_t lds_tris, lds_tri_meta;
+};
+
+// One ray-query launch (rtg_intersect; kernels in rtg_query.hip), passed by value after the DevScene.
+struct DevQuery {
+  const float4* rays;   // 2 per ray: {origin, tmin}, {dir, tmax}
+  const float* times;   // one per ray, or null: 0 for every ray
+  float4* hits;         // 2 per ray: {t, prim, u, v}, {normal, front_face}
+  // [0] rays answered, [3] hits, [4] stack overflow, [5] bad BVH code, [6] the ray cursor (the scene's
+  // counters, as DevJob::counters)
+  unsigned long long* counters;
+  const int32_t* prim_index;  // input index of each sphere, quad and triangle slot (HostScene::prim_index)
+  int32_t* spill;         // traversal-stack entries beyond the LDS part: [wave][depth][lane]
+  uint32_t num_rays;      // < 2^31
+  int32_t spill_depth;    // entries per lane in `spill` (0: the LDS stack suffices)
+  int32_t lds_stack;      // stack entries per lane kept in LDS (<= kLdsStack)
+  int32_t refill_batch;   // of 64 live lanes: finished lanes that start a write-out and refill pass
+  int32_t block;          // rays a wave reserves from the cursor with one atomicAdd (a multiple of 64)
+  int32_t leaf_batch;     // run a leaf trip once this many lanes wait at a leaf
+  // persistent kernels: byte offsets in dynamic LDS (lds_tri_meta -1: cold records through the caches)
+  int32_t lds_nodes, lds_stacks, lds_spheres, lds_quads, lds_tris, lds_tri_meta, lds_refs;
 };
 
 }  // namespace rtg

@@ -28,6 +28,7 @@ RTG_MAT_LAMBERTIAN, RTG_MAT_METAL, RTG_MAT_DIELECTRIC, RTG_MAT_DIFFUSE_LIGHT = 1
 RTG_TEX_SOLID, RTG_TEX_CHECKER, RTG_TEX_IMAGE, RTG_TEX_NOISE = 1, 2, 3, 4
 RTG_BVH_MEDIAN, RTG_BVH_SAH, RTG_BVH_GPU = 0, 1, 3
 RTG_RENDER_OUT_DEVICE, RTG_RENDER_ASYNC, RTG_RENDER_COUNT = 0x1, 0x2, 0x4
+RTG_QUERY_ANY, RTG_QUERY_DEVICE, RTG_QUERY_ASYNC = 0x1, 0x2, 0x4
 
 
 def RTG_RENDER_SCHEDULE(n: int) -> int:  # diagnostic kernel-schedule selector (include/rtgpu.h)
@@ -127,6 +128,30 @@ class rtg_launch_plan(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved_"}
 
 
+class rtg_ray(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("tmin", C.c_float), ("dir", C.c_float * 3), ("tmax", C.c_float)]
+
+
+class rtg_hit(C.Structure):
+    _fields_ = [("t", C.c_float), ("prim", C.c_int32), ("u", C.c_float), ("v", C.c_float),
+                ("normal", C.c_float * 3), ("front_face", C.c_int32)]
+
+
+class rtg_query_desc(C.Structure):
+    _fields_ = [("rays", C.c_void_p), ("times", C.c_void_p), ("num_rays", C.c_int64), ("hits", C.c_void_p),
+                ("flags", C.c_int32), ("max_workgroups", C.c_int32), ("stream", C.c_void_p)]
+
+
+class rtg_query_stats(C.Structure):
+    _fields_ = [("rays", C.c_uint64), ("hits", C.c_uint64), ("kernel_ms", C.c_double),
+                ("reserved_", C.c_uint64 * 5)]
+
+
+# numpy views of rtg_ray / rtg_hit (DeviceScene.intersect takes and returns these)
+RAY_DTYPE = [("origin", "<f4", 3), ("tmin", "<f4"), ("dir", "<f4", 3), ("tmax", "<f4")]
+HIT_DTYPE = [("t", "<f4"), ("prim", "<i4"), ("u", "<f4"), ("v", "<f4"), ("normal", "<f4", 3), ("front_face", "<i4")]
+
+
 class rtg_bvh_node_host(C.Structure):
     _fields_ = [("lo", (C.c_double * 3) * 2), ("hi", (C.c_double * 3) * 2),
                 ("child", C.c_int32 * 2), ("count", C.c_int32 * 2)]
@@ -146,7 +171,7 @@ RTG_SYMBOLS = ("rtg_abi_version", "rtg_last_error", "rtg_device_count", "rtg_cam
                "rtg_gather_rows", "rtg_deinterleave_rows", "rtg_render_frame", "rtg_render_plan",
                "rtg_shard_layout", "rtg_deinterleave_rows_host", "rtg_scene_prepare",
                "rtg_hot_treelet_order_host", "rtg_bvh_node_order",
-               "rtg_allocation_count")
+               "rtg_allocation_count", "rtg_intersect")
 RTG_COMM_ID_BYTES = 128
 
 
@@ -231,12 +256,13 @@ class Library:
         L.rtg_deinterleave_rows_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64]
         L.rtg_bvh_node_order.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
         L.rtg_allocation_count.argtypes = [_P(C.c_uint64), _P(C.c_uint64)]
+        L.rtg_intersect.argtypes = [C.c_void_p, _P(rtg_query_desc), _P(rtg_query_stats)]
         for name in ("rtg_device_count", "rtg_camera_resolve", "rtg_scene_create",
                      "rtg_scene_get_info", "rtg_render", "rtg_render_wait", "rtg_resolve_rgb8",
                      "rtg_bvh_build_host", "rtg_comm_create_local", "rtg_comm_unique_id",
                      "rtg_comm_create_rank", "rtg_comm_size", "rtg_gather_rows", "rtg_deinterleave_rows",
                      "rtg_render_frame", "rtg_render_plan", "rtg_shard_layout", "rtg_deinterleave_rows_host",
-                     "rtg_bvh_node_order", "rtg_allocation_count"):
+                     "rtg_bvh_node_order", "rtg_allocation_count", "rtg_intersect"):
             getattr(L, name).restype = C.c_int32
         if L.rtg_abi_version() != RTG_ABI_VERSION:
             raise RuntimeError("librtgpu ABI version mismatch")
@@ -478,6 +504,37 @@ class DeviceScene:
         self.L.check("rtg_render", self.L.lib.rtg_render(self.handle, C.byref(cam), C.byref(job),
                                                           C.c_void_p(out_ptr) if out_ptr else None,
                                                           C.byref(st)))
+        return st
+
+    def intersect(self, rays, times=None, any_hit: bool = False, schedule: int = 0, max_workgroups: int = 0):
+        """Batched ray query (rtgpu.h rtg_intersect): `rays` a numpy array of RAY_DTYPE, `times` float32 per ray
+        or None; returns (hits, stats), hits a numpy array of HIT_DTYPE. any_hit: occlusion query."""
+        import numpy as np
+
+        rays = np.ascontiguousarray(rays, dtype=np.dtype(RAY_DTYPE))
+        hits = np.zeros(rays.shape[0], dtype=np.dtype(HIT_DTYPE))
+        if times is not None:
+            times = np.ascontiguousarray(times, dtype=np.float32)
+            if times.shape != (rays.shape[0],):
+                raise ValueError("times must hold one float per ray")
+        q = rtg_query_desc(rays.ctypes.data, times.ctypes.data if times is not None else None, rays.shape[0],
+                           hits.ctypes.data, (RTG_QUERY_ANY if any_hit else 0) | RTG_RENDER_SCHEDULE(schedule),
+                           max_workgroups, None)
+        st = rtg_query_stats()
+        self.L.check("rtg_intersect", self.L.lib.rtg_intersect(self.handle, C.byref(q), C.byref(st)))
+        return hits, st
+
+    def intersect_device(self, rays_ptr: int, num_rays: int, hits_ptr: int, times_ptr: int = 0,
+                         stream_ptr: Optional[int] = None, any_hit: bool = False, schedule: int = 0,
+                         max_workgroups: int = 0, asynchronous: bool = False) -> rtg_query_stats:
+        """The same on device memory of the scene's device (32-byte rtg_ray / rtg_hit records), on `stream_ptr`
+        (hipStream_t); asynchronous: returns once enqueued."""
+        flags = RTG_QUERY_DEVICE | (RTG_QUERY_ANY if any_hit else 0) | (RTG_QUERY_ASYNC if asynchronous else 0)
+        q = rtg_query_desc(C.c_void_p(rays_ptr), C.c_void_p(times_ptr) if times_ptr else None, num_rays,
+                           C.c_void_p(hits_ptr), flags | RTG_RENDER_SCHEDULE(schedule), max_workgroups,
+                           C.c_void_p(stream_ptr) if stream_ptr else None)
+        st = rtg_query_stats()
+        self.L.check("rtg_intersect", self.L.lib.rtg_intersect(self.handle, C.byref(q), C.byref(st)))
         return st
 
     def wait(self) -> rtg_render_stats:

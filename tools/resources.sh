@@ -1,8 +1,15 @@
 #!/bin/bash
 # tools/resources.sh — per-kernel VGPR / SGPR / scratch / occupancy of rtg_kernels.hip (gfx950)
 cd "$(dirname "$0")/.."
+# RES_QUERY=1: the ray-query kernels (rtg_query.hip) with the Makefile's flags for them instead
+src=rtg_kernels.hip
+extra=
+if [ -n "${RES_QUERY:-}" ]; then
+  src=rtg_query.hip
+  extra="-fPIC -Xclang -target-feature -Xclang -packed-fp32-ops"
+fi
 /opt/rocm/bin/hipcc -std=c++17 -O3 --offload-arch=gfx950 -ffp-contract=off -fno-slp-vectorize -Iinclude \
-  -Iraytracing-practice_amd/csrc ${RES_DEFS:-} -c raytracing-practice_amd/csrc/rtg_kernels.hip -o /tmp/rtg_res.o \
+  -Iraytracing-practice_amd/csrc ${RES_DEFS:-} $extra -c raytracing-practice_amd/csrc/$src -o /tmp/rtg_res.o \
   -Rpass-analysis=kernel-resource-usage 2>&1 |
   python3 -c '
 import re, sys
