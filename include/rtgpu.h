@@ -108,6 +108,11 @@ typedef struct rtg_perlin {
 #define RTG_BVH_SAH 1    /* binned SAH, leaves of <= 4 primitives, collapsed to 4-wide nodes */
 #define RTG_BVH_GPU 3    /* built on the device: Morton-code LBVH (Karras) collapsed to 4-wide nodes;
                             milliseconds for 1M primitives, more traversal steps than SAH */
+/* May be or-ed into bvh_mode with any of the three: the scene keeps on the device what rtg_scene_update needs
+ * (each triangle slot's vertex box, the input-index-to-slot table, a parent and a counter word per node).
+ * rtg_scene_info.bvh_mode reports the mode with the bit; rtg_bvh_build_host ignores it. Scenes created without
+ * it are exactly what they were: same device bytes, allocations and kernels. */
+#define RTG_BVH_REFIT 0x100
 
 typedef struct rtg_scene_desc {
   uint32_t abi_version; /* RTG_ABI_VERSION (6 is still accepted: it has no tie_rank, read as NULL) */
@@ -426,6 +431,64 @@ typedef struct rtg_query_stats {
   uint64_t reserved_[5]; /* [0] schedule run, [1] workgroups, [2] waves per workgroup, [3] LDS bytes per workgroup */
 } rtg_query_stats;
 rtg_status rtg_intersect(rtg_scene* scene, const rtg_query_desc* q, rtg_query_stats* stats);
+
+/* ---- scene updates (ABI 7, additive): moving geometry without a rebuild ----
+ * rtg_scene_update gives `count` primitives of a scene created with RTG_BVH_REFIT new coordinates and refits every
+ * node box of the existing tree on the device. A primitive's kind and material, the tree's topology, the leaf
+ * references, the slots, the tie ranks and the schedule choice do not change.
+ *  - Fields: rtg_prim_update's have the meaning of rtg_primitive's (a sphere takes both centres and the radius, a
+ *    quad or triangle Q, u, v). indices are input primitive indices (into rtg_scene_desc.prims) and must be
+ *    distinct (not checked); indices == NULL means prims[i] is primitive i and count == num_prims (the whole-mesh
+ *    case, coalesced reads). RTG_UPDATE_DEVICE: both arrays are device pointers on the scene's device.
+ *  - Records: after the call each updated primitive's device record is bit-identical to what rtg_scene_create
+ *    writes for an rtg_primitive whose doubles equal the given floats: the sphere and quad records, the triangle's
+ *    plane form and its vertex box are formed in fp64 (no contraction) from the widened floats in compile_scene's
+ *    order and rounded once. Closest-hit t, winner, u, v, normal and a render's frame depend only on records and
+ *    tie ranks, not on the tree, so an updated scene answers exactly as a freshly created scene of the moved
+ *    primitives does.
+ *  - Boxes: after the call every child box of every node contains the culling boxes (DESIGN.md §4 "conservative
+ *    culling", as the device builder computes them) of the primitives below it, for the scene's M. M never
+ *    shrinks: it becomes max(current, largest |coordinate| of the updated primitives' boxes), computed on the host
+ *    for host pointers, by a device reduction and one read-back for device pointers (stats.origin_bound). The tile
+ *    order and the hot-treelet node order are kept: they are performance hints and stay valid.
+ *  - The occluder (a scene-spanning sphere kept out of the tree) is updatable: only its record changes.
+ *  - Errors: the descriptor is validated before the scene is looked at, and everything before any device work:
+ *    NULL, a negative count, unknown flags, a NULL array with count > 0 are RTG_E_INVALID; then a scene without
+ *    RTG_BVH_REFIT is RTG_E_UNSUPPORTED; indices == NULL with count != num_prims and a host index out of range are
+ *    RTG_E_INVALID. count == 0 is RTG_OK and launches nothing. A triangle with |u x v| == 0, a non-finite value or
+ *    a coordinate reach of 1e30 or more: with host pointers RTG_E_INVALID and nothing changes; with device pointers
+ *    that primitive (as one whose index is out of range) keeps its old record and is counted in stats.invalid, the
+ *    rest is applied and the tree refitted, so the scene stays consistent, and the call returns RTG_E_INVALID.
+ *  - Ordering: not concurrent with renders or queries of the same scene (a render not waited for is
+ *    RTG_E_INVALID); like rtg_intersect it first waits for a query still in flight. Runs on `stream` (NULL: the
+ *    scene's own) and is complete when it returns.
+ *  - Allocation: host batches go through the scene's grow-only pinned staging and query staging buffers; once
+ *    they reached a batch's size updates allocate nothing (rtg_allocation_count).
+ *  - Tree quality: a refit keeps the topology, so traversal cost grows as geometry moves away from where the tree
+ *    was built (DESIGN.md §8 "Scene updates"); the remedy is to create the scene again. */
+typedef struct rtg_prim_update {
+  float p0[3];
+  float radius;
+  float p1[3];
+  float pad0_;
+  float p2[3];
+  float pad1_;
+} rtg_prim_update; /* 48 B */
+#define RTG_UPDATE_DEVICE 0x1 /* indices / prims are device pointers on the scene's device */
+typedef struct rtg_update_desc {
+  const int32_t* indices; /* NULL: prims[i] is primitive i, count == num_prims */
+  const rtg_prim_update* prims;
+  int64_t count;
+  int32_t flags;
+  void* stream; /* hipStream_t, NULL: the scene's own stream */
+} rtg_update_desc;
+typedef struct rtg_update_stats {
+  uint64_t updated, invalid;
+  double kernel_ms;    /* the record kernel plus the refit kernels (HIP events) */
+  double origin_bound; /* M after the call */
+  uint64_t reserved_[4];
+} rtg_update_stats;
+rtg_status rtg_scene_update(rtg_scene* scene, const rtg_update_desc* u, rtg_update_stats* stats);
 
 /* ---- multi-GPU frames: row-interleaved shards, one RCCL gather over xGMI ----
  * Replaces the reference's single-device pixel loop of camera::render (camera.hpp:29-72) when the

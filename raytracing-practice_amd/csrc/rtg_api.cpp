@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "rtg_internal.hpp"
+#include "rtg_refit.hpp"
 
 namespace rtg {
 hipError_t launch_combine(const float* partial, float* out, int64_t n_pixels, int chunks, float scale,
@@ -681,7 +682,7 @@ bool compile_scene(const rtg_scene_desc* d, HostScene* out, std::string* err) {
         out->tris.insert(out->tris.end(), rec, rec + 12);
         out->tri_meta.push_back(p.material);
         out->tri_meta.push_back(static_cast<int32_t>(tie_rank(pid)));
-        if (gpu_bvh) {  // the device builder's view of the triangle: its vertex box
+        if (gpu_bvh || out->refit) {  // the device builder's (and a refit's) view of the triangle: its vertex box
           double lo[3], hi[3];
           prim_bbox(p, lo, hi);
           const float b6[6] = {round_down(lo[0]), round_down(lo[1]), round_down(lo[2]),
@@ -1000,6 +1001,18 @@ struct rtg_scene {
   ScratchBuf scr_query;
   bool query_pending = false;
   hipStream_t query_stream = nullptr;
+  // scene updates (RTG_BVH_REFIT; rtg_scene_update): one allocation of the slot of every input primitive (with
+  // the kind bits of a leaf reference; host copy too), the triangles' vertex boxes, a parent and an arrival
+  // word per node and the update kernel's two result words; two more events time the refit launches
+  bool refit = false;
+  void* refit_mem = nullptr;
+  std::vector<int32_t> slot_of;
+  int32_t* slot_of_dev = nullptr;
+  float* tri_boxes = nullptr;
+  int32_t* node_parent = nullptr;
+  uint32_t* node_arrived = nullptr;
+  unsigned long long* update_words = nullptr;
+  hipEvent_t ev2 = nullptr, ev3 = nullptr;
   // deferred (async) render state
   bool pending = false;
   hipStream_t pending_stream = nullptr;
@@ -1041,7 +1054,9 @@ rtg_status rtg_bvh_build_host(const rtg_scene_desc* desc, rtg_bvh_node_host* nod
     return fail(RTG_E_INVALID, "malformed primitive array");
   Bvh bvh;
   std::string err;
-  if (!build_bvh(desc, &bvh, &err)) return fail(RTG_E_INVALID, err);
+  rtg_scene_desc plain = *desc;  // RTG_BVH_REFIT changes nothing of the tree
+  plain.bvh_mode &= ~RTG_BVH_REFIT;
+  if (!build_bvh(&plain, &bvh, &err)) return fail(RTG_E_INVALID, err);
   if (num_nodes) *num_nodes = static_cast<int64_t>(bvh.nodes.size());
   if (num_refs) *num_refs = static_cast<int64_t>(bvh.refs.size());
   if (depth) *depth = bvh.depth;
@@ -1092,9 +1107,13 @@ rtg_status rtg_scene_create(const rtg_scene_desc* desc_in, int32_t device, rtg_s
   std::memcpy(&desc_v, desc_in,
               desc_in->abi_version == 6 ? offsetof(rtg_scene_desc, tie_rank) : sizeof(rtg_scene_desc));
   const rtg_scene_desc* desc = &desc_v;
+  // RTG_BVH_REFIT rides on the mode: the builders see the plain mode (any other unknown bit stays invalid there)
+  const bool refit = (desc_v.bvh_mode & RTG_BVH_REFIT) != 0;
+  desc_v.bvh_mode &= ~RTG_BVH_REFIT;
   // validate + compile first (host only), so malformed scenes report RTG_E_INVALID anywhere
   const auto t0 = std::chrono::steady_clock::now();
   HostScene hs;
+  hs.refit = refit;
   std::string err;
   if (!compile_scene(desc, &hs, &err)) return fail(RTG_E_INVALID, err);
   if (hs.stack_need > kMaxStackNeed)
@@ -1196,6 +1215,42 @@ rtg_status rtg_scene_create(const rtg_scene_desc* desc_in, int32_t device, rtg_s
         return cleanup(hip_fail(e, "hipStreamSynchronize(upload)"));
     }
   }
+  // RTG_BVH_REFIT: what rtg_scene_update needs, uploaded now (a frozen scene allocates none of it)
+  size_t refit_bytes = 0;
+  if (refit) {
+    if (hs.prim_index.empty() && hs.num_prims > 0)
+      return cleanup(fail(RTG_E_UNSUPPORTED, "RTG_BVH_REFIT needs fewer than 2^31 primitives"));
+    const int64_t nsph = static_cast<int64_t>(hs.spheres.size() / 8), nquad = static_cast<int64_t>(hs.quads.size() / 20);
+    s->slot_of.assign(static_cast<size_t>(hs.num_prims), -1);
+    for (size_t k = 0; k < hs.prim_index.size(); ++k) {  // the inverse of the slot table (spheres, quads, triangles)
+      const int64_t i = static_cast<int64_t>(k);
+      const int32_t ref = i < nsph ? static_cast<int32_t>(i)
+                          : i < nsph + nquad ? (static_cast<int32_t>(i - nsph) | kQuadRefBit)
+                                             : (static_cast<int32_t>(i - nsph - nquad) | kTriRefBit);
+      if (hs.prim_index[k] >= 0) s->slot_of[hs.prim_index[k]] = ref;
+    }
+    const int64_t node_cap = hs.gpu_bvh ? hs.node_capacity : hs.num_nodes;
+    auto pad256 = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t o_slot = 0, o_box = pad256(s->slot_of.size() * 4), o_par = o_box + pad256(hs.tri_boxes.size() * 4);
+    const size_t o_arr = o_par + pad256(node_cap * 4), o_words = o_arr + pad256(node_cap * 4);
+    refit_bytes = o_words + 256;
+    if ((e = dev_alloc(&s->refit_mem, refit_bytes)) != hipSuccess) return cleanup(hip_fail(e, "hipMalloc(refit tables)"));
+    char* rb = static_cast<char*>(s->refit_mem);
+    s->slot_of_dev = reinterpret_cast<int32_t*>(rb + o_slot);
+    s->tri_boxes = reinterpret_cast<float*>(rb + o_box);
+    s->node_parent = reinterpret_cast<int32_t*>(rb + o_par);
+    s->node_arrived = reinterpret_cast<uint32_t*>(rb + o_arr);
+    s->update_words = reinterpret_cast<unsigned long long*>(rb + o_words);
+    if (!s->slot_of.empty())
+      e = hipMemcpyAsync(s->slot_of_dev, s->slot_of.data(), s->slot_of.size() * 4, hipMemcpyHostToDevice, s->own_stream);
+    if (e == hipSuccess && !hs.tri_boxes.empty())
+      e = hipMemcpyAsync(s->tri_boxes, hs.tri_boxes.data(), hs.tri_boxes.size() * 4, hipMemcpyHostToDevice, s->own_stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->own_stream);
+    if (e != hipSuccess) return cleanup(hip_fail(e, "hipMemcpy(refit tables)"));
+    if ((e = hipEventCreate(&s->ev2)) != hipSuccess || (e = hipEventCreate(&s->ev3)) != hipSuccess)
+      return cleanup(hip_fail(e, "hipEventCreate"));
+    s->refit = true;
+  }
   const auto t2 = std::chrono::steady_clock::now();
   double gpu_build_ms = 0.0;
   const int64_t nrefs = static_cast<int64_t>(hs.refs.size());
@@ -1206,7 +1261,9 @@ rtg_status rtg_scene_create(const rtg_scene_desc* desc_in, int32_t device, rtg_s
       return cleanup(hip_fail(e, "hipMalloc(bvh refs)"));
     // the triangles' vertex boxes, for the build only (their plane-form records do not hold the vertices)
     float* tri_boxes = nullptr;
-    if (!hs.tri_boxes.empty()) {
+    if (refit) {
+      tri_boxes = s->tri_boxes;  // kept with the scene
+    } else if (!hs.tri_boxes.empty()) {
       e = dev_alloc_async(reinterpret_cast<void**>(&tri_boxes), hs.tri_boxes.size() * 4, s->own_stream);
       if (e == hipSuccess)
         e = hipMemcpyAsync(tri_boxes, hs.tri_boxes.data(), hs.tri_boxes.size() * 4, hipMemcpyHostToDevice, s->own_stream);
@@ -1221,7 +1278,7 @@ rtg_status rtg_scene_create(const rtg_scene_desc* desc_in, int32_t device, rtg_s
       e = hipMemcpyAsync(refs_dev, sorted, nrefs * 4, hipMemcpyDeviceToDevice, s->own_stream);
     const hipError_t ef = hipFreeAsync(sorted, s->own_stream);
     if (e == hipSuccess) e = ef;
-    if (tri_boxes) {
+    if (tri_boxes && !refit) {
       const hipError_t et = hipFreeAsync(tri_boxes, s->own_stream);
       if (e == hipSuccess) e = et;
     }
@@ -1295,13 +1352,13 @@ rtg_status rtg_scene_create(const rtg_scene_desc* desc_in, int32_t device, rtg_s
   s->origin_bound = hs.origin_bound;
   s->prim_index = std::move(hs.prim_index);
   s->info.device = device;
-  s->info.bvh_mode = desc->bvh_mode;
+  s->info.bvh_mode = desc->bvh_mode | (refit ? RTG_BVH_REFIT : 0);
   s->info.num_prims = hs.num_prims;
   s->info.num_nodes = hs.num_nodes;
   s->info.bvh_depth = hs.depth;
   s->info.stack_depth = hs.stack_need;
   s->stack_need = hs.stack_need;
-  s->info.device_bytes = static_cast<int64_t>(total);
+  s->info.device_bytes = static_cast<int64_t>(total + refit_bytes);
   s->info.build_ms = std::chrono::duration<double, std::milli>(t1 - t0).count() + gpu_build_ms;
   s->info.upload_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
   s->info.bvh_ms = hs.bvh_ms + gpu_build_ms;
@@ -1330,6 +1387,9 @@ void rtg_scene_destroy(rtg_scene* s) {
   if (s->order_dev) (void)hipFree(s->order_dev);
   if (s->query_pending && s->query_stream) (void)hipStreamSynchronize(s->query_stream);
   if (s->prim_index_dev) (void)hipFree(s->prim_index_dev);
+  if (s->refit_mem) (void)hipFree(s->refit_mem);
+  if (s->ev2) (void)hipEventDestroy(s->ev2);
+  if (s->ev3) (void)hipEventDestroy(s->ev3);
   for (ScratchBuf* b : {&s->scr_spill, &s->scr_trace, &s->scr_partial, &s->scr_query})
     if (b->p) (void)hipFree(b->p);
   if (s->ev0) (void)hipEventDestroy(s->ev0);
@@ -2409,6 +2469,144 @@ rtg_status rtg_intersect(rtg_scene* s, const rtg_query_desc* q, rtg_query_stats*
   if (s->host_counters[0] != static_cast<unsigned long long>(n))
     return fail(RTG_E_HIP, "the query answered " + std::to_string(s->host_counters[0]) + " of " + std::to_string(n) + " rays");
   if (!dev) std::memcpy(q->hits, s->host_stage, ray_bytes);
+  return RTG_OK;
+}
+
+rtg_status rtg_scene_update(rtg_scene* s, const rtg_update_desc* u, rtg_update_stats* stats) {
+  // the descriptor first, then the scene (rtgpu.h); everything before any device work
+  if (!u) return fail(RTG_E_INVALID, "null update descriptor");
+  if (stats) *stats = rtg_update_stats{};
+  if (u->count < 0) return fail(RTG_E_INVALID, "count is negative");
+  if (u->flags & ~RTG_UPDATE_DEVICE) return fail(RTG_E_INVALID, "unknown update flags");
+  if (u->count > 0 && !u->prims) return fail(RTG_E_INVALID, "null primitive array");
+  if (!s) return fail(RTG_E_INVALID, "null scene");
+  if (s->pending) return fail(RTG_E_INVALID, "a previous async render was not waited for");
+  if (!s->refit) return fail(RTG_E_UNSUPPORTED, "the scene was created without RTG_BVH_REFIT");
+  if (stats) stats->origin_bound = s->origin_bound;
+  if (u->count == 0) return RTG_OK;  // nothing to launch
+  const int64_t n = u->count, np = s->info.num_prims;
+  const bool dev = (u->flags & RTG_UPDATE_DEVICE) != 0;
+  if (!u->indices && n != np) return fail(RTG_E_INVALID, "indices is NULL and count is not the scene's primitive count");
+  if (n > np) return fail(RTG_E_INVALID, "more updates than primitives (indices must be distinct)");
+  double reach = 0.0;
+  if (!dev) {  // the kernel's own rejections, on the host: a bad batch changes nothing
+    for (int64_t k = 0; k < n; ++k) {
+      const int64_t i = u->indices ? u->indices[k] : k;
+      if (i < 0 || i >= np) return fail(RTG_E_INVALID, "update index out of range at " + std::to_string(k));
+      const rtg_prim_update& pu = u->prims[k];
+      const int32_t ref = s->slot_of[i];
+      rtg_primitive p{};
+      p.kind = (ref & kTriRefBit) ? RTG_PRIM_TRIANGLE : (ref & kQuadRefBit) ? RTG_PRIM_QUAD : RTG_PRIM_SPHERE;
+      p.radius = pu.radius;
+      bool ok = ref >= 0;
+      for (int a = 0; a < 3; ++a) {
+        p.p0[a] = pu.p0[a], p.p1[a] = pu.p1[a], p.p2[a] = pu.p2[a];
+        ok = ok && std::isfinite(pu.p0[a]) && std::isfinite(pu.p1[a]) && (p.kind == RTG_PRIM_SPHERE || std::isfinite(pu.p2[a]));
+      }
+      if (p.kind == RTG_PRIM_SPHERE) ok = ok && std::isfinite(pu.radius);
+      if (ok && p.kind == RTG_PRIM_TRIANGLE) {
+        const D3 c = cross(d3(p.p1), d3(p.p2));
+        if (!(dot(c, c) > 0.0)) return fail(RTG_E_INVALID, "degenerate triangle (|u x v| == 0) at update " + std::to_string(k));
+      }
+      double lo[3], hi[3], m = 0.0;
+      if (ok) prim_bbox(p, lo, hi);
+      for (int a = 0; ok && a < 3; ++a) m = std::max({m, std::fabs(lo[a]), std::fabs(hi[a])});
+      if (!ok || !(m < 1e30)) return fail(RTG_E_INVALID, "update " + std::to_string(k) + " is not finite (or reaches 1e30)");
+      reach = std::max(reach, m);
+    }
+  }
+  RTG_HIP(hipSetDevice(s->device), "hipSetDevice");
+  rtg_status st = finish_query(s);
+  if (st != RTG_OK) return st;
+  hipStream_t stream = u->stream ? static_cast<hipStream_t>(u->stream) : s->own_stream;
+  SyncOnError sync_on_error;
+  sync_on_error.stream = stream;
+  UpdateArgs ua{};
+  ua.indices = u->indices;
+  ua.prims = reinterpret_cast<const float4*>(u->prims);
+  if (!dev) {  // pinned staging (the scene's host_stage), one DMA: prims | indices in the query staging buffer
+    const size_t prim_bytes = static_cast<size_t>(n) * sizeof(rtg_prim_update), idx_bytes = u->indices ? static_cast<size_t>(n) * 4 : 0;
+    if (s->host_stage_bytes < prim_bytes + idx_bytes) {
+      if (s->host_stage) RTG_HIP(hipHostFree(s->host_stage), "hipHostFree(stage)");
+      s->host_stage = nullptr;
+      s->host_stage_bytes = 0;
+      RTG_HIP(host_alloc(&s->host_stage, prim_bytes + idx_bytes), "hipHostMalloc(stage)");
+      s->host_stage_bytes = prim_bytes + idx_bytes;
+    }
+    if (s->scr_query.bytes < prim_bytes + idx_bytes) {
+      if (s->scr_query.p) RTG_HIP(hipFree(s->scr_query.p), "hipFree(scratch)");  // device-synchronous
+      s->scr_query = ScratchBuf{};
+      RTG_HIP(dev_alloc(&s->scr_query.p, prim_bytes + idx_bytes), "hipMalloc(update staging)");
+      s->scr_query.bytes = prim_bytes + idx_bytes;
+    }
+    char* stage = static_cast<char*>(s->host_stage);
+    std::memcpy(stage, u->prims, prim_bytes);
+    if (u->indices) std::memcpy(stage + prim_bytes, u->indices, idx_bytes);
+    RTG_HIP(hipMemcpyAsync(s->scr_query.p, stage, prim_bytes + idx_bytes, hipMemcpyHostToDevice, stream), "hipMemcpy(updates)");
+    ua.prims = static_cast<const float4*>(s->scr_query.p);
+    ua.indices = u->indices ? reinterpret_cast<const int32_t*>(static_cast<char*>(s->scr_query.p) + prim_bytes) : nullptr;
+  }
+  ua.count = n;
+  ua.num_prims = np;
+  ua.slot_of = s->slot_of_dev;
+  ua.spheres = const_cast<float4*>(s->dev.spheres);
+  ua.quads = const_cast<float4*>(s->dev.quads);
+  ua.tris = const_cast<float4*>(s->dev.tris);
+  ua.tri_boxes = s->tri_boxes;
+  ua.num_spheres = s->dev.num_spheres;
+  ua.num_quads = s->dev.num_quads;
+  ua.num_tris = s->dev.num_tris;
+  ua.words = s->update_words;
+  RTG_HIP(hipMemsetAsync(s->update_words, 0, 16, stream), "hipMemsetAsync");
+  RTG_HIP(hipEventRecord(s->ev0, stream), "hipEventRecord");
+  RTG_HIP(launch_update_records(ua, stream), "update kernel launch");
+  RTG_HIP(hipEventRecord(s->ev1, stream), "hipEventRecord");
+  uint64_t invalid = 0;
+  if (dev) {  // the batch's reach and rejections: one read-back, the wait rtg_intersect takes for its origin reach
+    RTG_HIP(hipMemcpyAsync(s->host_counters, s->update_words, 16, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(reach)");
+    RTG_HIP(hipStreamSynchronize(stream), "update kernel");
+    std::memcpy(&reach, &s->host_counters[0], 8);
+    invalid = s->host_counters[1];
+  }
+  // M only grows. The refit computes every box anew from the records, so M needs no headroom: the pads take
+  // round_up(M), as the device builder's do
+  if (reach > s->origin_bound) s->origin_bound = reach;
+  RefitArgs ra{};
+  ra.nodes = reinterpret_cast<float*>(const_cast<float4*>(s->dev.nodes));
+  ra.num_nodes = s->dev.num_nodes;
+  ra.refs = s->dev.refs;
+  ra.num_refs = s->dev.num_refs;
+  ra.spheres = s->dev.spheres;
+  ra.quads = s->dev.quads;
+  ra.tri_boxes = s->tri_boxes;
+  ra.num_spheres = s->dev.num_spheres;
+  ra.num_quads = s->dev.num_quads;
+  ra.num_tris = s->dev.num_tris;
+  ra.pads = cull_pads(round_up(s->origin_bound));
+  ra.parent = s->node_parent;
+  ra.arrived = s->node_arrived;
+  RTG_HIP(hipEventRecord(s->ev2, stream), "hipEventRecord");
+  RTG_HIP(launch_refit(ra, s->dev.node_width, stream), "refit kernel launch");
+  RTG_HIP(hipEventRecord(s->ev3, stream), "hipEventRecord");
+  s->host_nodes.clear();  // the hot treelet downloads the refitted array when it next tunes
+  sync_on_error.committed = true;
+  RTG_HIP(hipStreamSynchronize(stream), "refit kernel");
+  float ms0 = 0.0f, ms1 = 0.0f;
+  RTG_HIP(hipEventElapsedTime(&ms0, s->ev0, s->ev1), "hipEventElapsedTime");
+  RTG_HIP(hipEventElapsedTime(&ms1, s->ev2, s->ev3), "hipEventElapsedTime");
+  if (stats) {
+    stats->updated = static_cast<uint64_t>(n) - invalid;
+    stats->invalid = invalid;
+    stats->kernel_ms = static_cast<double>(ms0) + ms1;
+    stats->origin_bound = s->origin_bound;
+    stats->reserved_[0] = static_cast<uint64_t>(ms0 * 1e6);  // ns of the record kernel (tools/update_bench.py)
+  }
+  if (s->knobs.verbose)
+    std::fprintf(stderr, "[rtg] update: %lld primitives (%llu invalid), records %.3f ms, refit of %lld nodes %.3f ms, M %.6g\n",
+                 static_cast<long long>(n), static_cast<unsigned long long>(invalid), ms0,
+                 static_cast<long long>(s->dev.num_nodes), ms1, s->origin_bound);
+  if (invalid != 0)
+    return fail(RTG_E_INVALID, std::to_string(invalid) + " updates were left out (degenerate triangle, non-finite value or bad index)");
   return RTG_OK;
 }
 

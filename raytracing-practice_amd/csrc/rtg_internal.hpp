@@ -42,9 +42,10 @@ struct HostScene {
   std::vector<float> quads;      // 20 floats per quad
   std::vector<float> tris;       // 12 floats per triangle (the hot record)
   std::vector<int32_t> tri_meta;  // 2 ints per triangle {material, tie rank} (the cold record)
-  // RTG_BVH_GPU only: each triangle slot's vertex box {lo.xyz, hi.xyz}, rounded outward (the plane-form
-  // records do not hold the vertices); uploaded for the device build, then dropped
+  // RTG_BVH_GPU and RTG_BVH_REFIT only: each triangle slot's vertex box {lo.xyz, hi.xyz}, rounded outward (the
+  // plane-form records do not hold the vertices); uploaded for the device build, then dropped, or kept for refits
   std::vector<float> tri_boxes;
+  bool refit = false;  // in: RTG_BVH_REFIT (set before compile_scene)
   std::vector<float> materials;  // 8 floats per material
   std::vector<float> textures;   // 8 floats per texture
   std::vector<int32_t> image_hdr;  // 4 ints per image

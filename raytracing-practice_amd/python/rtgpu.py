@@ -27,8 +27,10 @@ RTG_PRIM_SPHERE, RTG_PRIM_QUAD, RTG_PRIM_TRIANGLE = 1, 2, 3
 RTG_MAT_LAMBERTIAN, RTG_MAT_METAL, RTG_MAT_DIELECTRIC, RTG_MAT_DIFFUSE_LIGHT = 1, 2, 3, 4
 RTG_TEX_SOLID, RTG_TEX_CHECKER, RTG_TEX_IMAGE, RTG_TEX_NOISE = 1, 2, 3, 4
 RTG_BVH_MEDIAN, RTG_BVH_SAH, RTG_BVH_GPU = 0, 1, 3
+RTG_BVH_REFIT = 0x100  # or-ed into bvh_mode: the scene can be updated (DeviceScene.update)
 RTG_RENDER_OUT_DEVICE, RTG_RENDER_ASYNC, RTG_RENDER_COUNT = 0x1, 0x2, 0x4
 RTG_QUERY_ANY, RTG_QUERY_DEVICE, RTG_QUERY_ASYNC = 0x1, 0x2, 0x4
+RTG_UPDATE_DEVICE = 0x1
 
 
 def RTG_RENDER_SCHEDULE(n: int) -> int:  # diagnostic kernel-schedule selector (include/rtgpu.h)
@@ -147,6 +149,23 @@ class rtg_query_stats(C.Structure):
                 ("reserved_", C.c_uint64 * 5)]
 
 
+class rtg_prim_update(C.Structure):
+    _fields_ = [("p0", C.c_float * 3), ("radius", C.c_float), ("p1", C.c_float * 3), ("pad0_", C.c_float),
+                ("p2", C.c_float * 3), ("pad1_", C.c_float)]
+
+
+class rtg_update_desc(C.Structure):
+    _fields_ = [("indices", C.c_void_p), ("prims", C.c_void_p), ("count", C.c_int64), ("flags", C.c_int32),
+                ("stream", C.c_void_p)]
+
+
+class rtg_update_stats(C.Structure):
+    _fields_ = [("updated", C.c_uint64), ("invalid", C.c_uint64), ("kernel_ms", C.c_double),
+                ("origin_bound", C.c_double), ("reserved_", C.c_uint64 * 4)]
+
+
+# numpy view of rtg_prim_update (DeviceScene.update also takes an (n, 12) float32 array of the same words)
+UPDATE_DTYPE = [("p0", "<f4", 3), ("radius", "<f4"), ("p1", "<f4", 3), ("pad0_", "<f4"), ("p2", "<f4", 3), ("pad1_", "<f4")]
 # numpy views of rtg_ray / rtg_hit (DeviceScene.intersect takes and returns these)
 RAY_DTYPE = [("origin", "<f4", 3), ("tmin", "<f4"), ("dir", "<f4", 3), ("tmax", "<f4")]
 HIT_DTYPE = [("t", "<f4"), ("prim", "<i4"), ("u", "<f4"), ("v", "<f4"), ("normal", "<f4", 3), ("front_face", "<i4")]
@@ -171,7 +190,7 @@ RTG_SYMBOLS = ("rtg_abi_version", "rtg_last_error", "rtg_device_count", "rtg_cam
                "rtg_gather_rows", "rtg_deinterleave_rows", "rtg_render_frame", "rtg_render_plan",
                "rtg_shard_layout", "rtg_deinterleave_rows_host", "rtg_scene_prepare",
                "rtg_hot_treelet_order_host", "rtg_bvh_node_order",
-               "rtg_allocation_count", "rtg_intersect")
+               "rtg_allocation_count", "rtg_intersect", "rtg_scene_update")
 RTG_COMM_ID_BYTES = 128
 
 
@@ -257,12 +276,13 @@ class Library:
         L.rtg_bvh_node_order.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
         L.rtg_allocation_count.argtypes = [_P(C.c_uint64), _P(C.c_uint64)]
         L.rtg_intersect.argtypes = [C.c_void_p, _P(rtg_query_desc), _P(rtg_query_stats)]
+        L.rtg_scene_update.argtypes = [C.c_void_p, _P(rtg_update_desc), _P(rtg_update_stats)]
         for name in ("rtg_device_count", "rtg_camera_resolve", "rtg_scene_create",
                      "rtg_scene_get_info", "rtg_render", "rtg_render_wait", "rtg_resolve_rgb8",
                      "rtg_bvh_build_host", "rtg_comm_create_local", "rtg_comm_unique_id",
                      "rtg_comm_create_rank", "rtg_comm_size", "rtg_gather_rows", "rtg_deinterleave_rows",
                      "rtg_render_frame", "rtg_render_plan", "rtg_shard_layout", "rtg_deinterleave_rows_host",
-                     "rtg_bvh_node_order", "rtg_allocation_count", "rtg_intersect"):
+                     "rtg_bvh_node_order", "rtg_allocation_count", "rtg_intersect", "rtg_scene_update"):
             getattr(L, name).restype = C.c_int32
         if L.rtg_abi_version() != RTG_ABI_VERSION:
             raise RuntimeError("librtgpu ABI version mismatch")
@@ -535,6 +555,34 @@ class DeviceScene:
                            C.c_void_p(stream_ptr) if stream_ptr else None)
         st = rtg_query_stats()
         self.L.check("rtg_intersect", self.L.lib.rtg_intersect(self.handle, C.byref(q), C.byref(st)))
+        return st
+
+    def update(self, indices, prims) -> rtg_update_stats:
+        """rtg_scene_update from host memory (scenes created with RTG_BVH_REFIT): `prims` an (n, 12) float32 array or
+        a numpy array of UPDATE_DTYPE, `indices` the input primitive index of each (int32, distinct), or None when
+        prims holds every primitive in input order."""
+        import numpy as np
+
+        prims = np.asarray(prims)
+        if prims.dtype != np.dtype(UPDATE_DTYPE):
+            prims = np.ascontiguousarray(prims, dtype=np.float32).reshape(-1, 12)
+        prims = np.ascontiguousarray(prims)
+        if indices is not None:
+            indices = np.ascontiguousarray(indices, dtype=np.int32)
+            if indices.shape != (prims.shape[0],):
+                raise ValueError("indices must hold one index per primitive update")
+        u = rtg_update_desc(indices.ctypes.data if indices is not None else None, prims.ctypes.data, prims.shape[0], 0, None)
+        st = rtg_update_stats()
+        self.L.check("rtg_scene_update", self.L.lib.rtg_scene_update(self.handle, C.byref(u), C.byref(st)))
+        return st
+
+    def update_device(self, indices_ptr: int, prims_ptr: int, count: int, stream_ptr: Optional[int] = None) -> rtg_update_stats:
+        """The same from device memory of the scene's device (a torch tensor's data_ptr(): int32 indices, or 0 for
+        the whole mesh in input order; 48-byte rtg_prim_update records), on `stream_ptr` (hipStream_t)."""
+        u = rtg_update_desc(C.c_void_p(indices_ptr) if indices_ptr else None, C.c_void_p(prims_ptr), count,
+                            RTG_UPDATE_DEVICE, C.c_void_p(stream_ptr) if stream_ptr else None)
+        st = rtg_update_stats()
+        self.L.check("rtg_scene_update", self.L.lib.rtg_scene_update(self.handle, C.byref(u), C.byref(st)))
         return st
 
     def wait(self) -> rtg_render_stats:

@@ -1,5 +1,6 @@
 #!/bin/bash
 # tools/resources.sh — per-kernel VGPR / SGPR / scratch / occupancy of rtg_kernels.hip (gfx950)
+# RES_REFIT=1: the scene-update kernels (rtg_refit.hip) with the Makefile's flags for them instead
 cd "$(dirname "$0")/.."
 # RES_QUERY=1: the ray-query kernels (rtg_query.hip) with the Makefile's flags for them instead
 src=rtg_kernels.hip
@@ -7,6 +8,10 @@ extra=
 if [ -n "${RES_QUERY:-}" ]; then
   src=rtg_query.hip
   extra="-fPIC -Xclang -target-feature -Xclang -packed-fp32-ops"
+fi
+if [ -n "${RES_REFIT:-}" ]; then
+  src=rtg_refit.hip
+  extra="-fPIC -fslp-vectorize -Xclang -target-feature -Xclang -packed-fp32-ops"
 fi
 /opt/rocm/bin/hipcc -std=c++17 -O3 --offload-arch=gfx950 -ffp-contract=off -fno-slp-vectorize -Iinclude \
   -Iraytracing-practice_amd/csrc ${RES_DEFS:-} $extra -c raytracing-practice_amd/csrc/$src -o /tmp/rtg_res.o \
