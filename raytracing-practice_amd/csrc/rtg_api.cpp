@@ -939,6 +939,28 @@ hipError_t host_alloc(void** p, size_t bytes) {
 
 }  // namespace rtg
 
+// DevOccluder of a sphere record {c0.xyz, r}, {dc.xyz, material} at sphere slot `index` (-1: no occluder): what
+// sphere_t (rtg_trav.hpp) computes from the record alone, by the same operations on the same operands (DESIGN.md
+// §4 "occluder constants"). A sphere whose velocity is not exactly zero keeps the general path (mode 0).
+DevOccluder occluder_constants(const float* rec, int32_t index) {
+  DevOccluder o{};
+  o.index = index;
+  if (index < 0) return o;
+  std::memcpy(&o.mat, rec + 7, 4);
+  o.r = rec[3];
+  if (!(rec[4] == 0.0f && rec[5] == 0.0f && rec[6] == 0.0f)) return o;  // moving (or NaN): sphere_t on the record
+  for (int a = 0; a < 3; ++a) {
+    // madd(time, dc, c0) = fmaf(time, +-0, c0) for every time in [0, 1) (ps.time is a uniform draw): the product
+    // is the velocity's own zero at any such time, so time 0 stands for all of them (a -0 centre under a +0
+    // velocity becomes +0, here as there)
+    o.c[a] = std::fmaf(0.0f, rec[4 + a], rec[a]);
+    o.cd[a] = static_cast<double>(o.c[a]);
+  }
+  o.r2 = static_cast<double>(o.r) * static_cast<double>(o.r);  // 24 x 24 bits: exact
+  o.mode = std::fabs(o.r) < kSphereF64Radius ? 1 : 2;
+  return o;
+}
+
 // Grow-only device scratch of a scene's renders (stack spill, wave trace, tile ring or chunk partial sums).
 // Renders of one scene never overlap — rtg_render refuses while one is pending, collect_stats waits for
 // its stream, a failed render waits for it (SyncOnError) — so a buffer is idle whenever a render starts,
@@ -1312,6 +1334,7 @@ rtg_status rtg_scene_create(const rtg_scene_desc* desc_in, int32_t device, rtg_s
   s->dev.num_nodes = hs.num_nodes;
   s->dev.root_code = 0;
   s->dev.occluder = hs.occluder;
+  s->dev.occ = occluder_constants(hs.occluder >= 0 ? hs.spheres.data() + size_t(hs.occluder) * 8 : nullptr, hs.occluder);
   s->dev.sphere_f4 = 2;
   s->dev.treelet_bytes = 0;  // set per render by the treelet schedule
   s->dev.treelet_lds = 0;
@@ -1483,7 +1506,8 @@ rtg_status plan_render(const rtg_scene* s, const rtg_camera_desc* cam, const rtg
   if (job->row_stride <= 0 || job->row_begin < 0) return fail(RTG_E_INVALID, "bad row range");
   P->dev_out = (job->flags & RTG_RENDER_OUT_DEVICE) != 0;
   P->async = (job->flags & RTG_RENDER_ASYNC) != 0;
-  P->count = (job->flags & RTG_RENDER_COUNT) != 0;
+  // the per-wave timeline (RTG_WAVE_TRACE) is compiled into the counting kernels only: a traced render runs them
+  P->count = (job->flags & RTG_RENDER_COUNT) != 0 || !K.wave_trace.empty();
   if (P->async && !P->dev_out) return fail(RTG_E_INVALID, "RTG_RENDER_ASYNC requires RTG_RENDER_OUT_DEVICE");
 
   resolve_camera(cam, &P->cp);
@@ -1734,7 +1758,6 @@ rtg_status plan_render(const rtg_scene* s, const rtg_camera_desc* cam, const rtg
     j4.lds_stacks = l4[8];
     j4.lds_ring = l4[9];
     j4.lds_tris = l4[10], j4.lds_tri_meta = l4[11];
-    j4.trace = nullptr;  // the per-wave timeline covers the main launch's waves only
   }
   P->j4 = j4;
   P->variant = variant;
@@ -2158,7 +2181,8 @@ rtg_status rtg_render(rtg_scene* s, const rtg_camera_desc* cam, const rtg_render
   const bool trace = !K.wave_trace.empty();
   int64_t trace_slots = 0;
   if (trace) {
-    trace_slots = int64_t(P.grid_waves);
+    // the main launch's waves, then the dual launch's second workgroups' (four waves on every CU)
+    trace_slots = int64_t(P.grid_waves) + (P.lds4 > 0 ? int64_t(s->num_cus) * 4 : 0);
     if ((pst = grow(s->scr_trace, trace_slots * 32, "hipMalloc(trace)")) != RTG_OK) return pst;
     dj.trace = static_cast<unsigned long long*>(s->scr_trace.p);
     RTG_HIP(hipMemsetAsync(dj.trace, 0, trace_slots * 32, stream), "hipMemset(trace)");
@@ -2191,6 +2215,7 @@ rtg_status rtg_render(rtg_scene* s, const rtg_camera_desc* cam, const rtg_render
     j4.spill = dj.spill;
     j4.partial = dj.partial;
     j4.ring_words = dj.ring_words;
+    j4.trace = dj.trace ? dj.trace + int64_t(P.grid_waves) * 4 : nullptr;
     // the aux launch must sit in a hardware queue of its own, or it only starts after the main launch
     // has drained (HIP shares its GPU_MAX_HW_QUEUES = 4 queues round-robin among a process's streams:
     // with RCCL or a second library's streams the two launches serialised, +10 %); high-priority
@@ -2588,9 +2613,17 @@ rtg_status rtg_scene_update(rtg_scene* s, const rtg_update_desc* u, rtg_update_s
   RTG_HIP(hipEventRecord(s->ev2, stream), "hipEventRecord");
   RTG_HIP(launch_refit(ra, s->dev.node_width, stream), "refit kernel launch");
   RTG_HIP(hipEventRecord(s->ev3, stream), "hipEventRecord");
+  // the occluder's record may be among the updated ones (the device wrote it, from device memory under
+  // RTG_UPDATE_DEVICE): its 32 bytes back, and its constants anew below (32 B into host_counters[4..7];
+  // [0..1] hold the batch's reach and rejections)
+  float* occ_rec = reinterpret_cast<float*>(s->host_counters + 4);
+  if (s->dev.occluder >= 0)
+    RTG_HIP(hipMemcpyAsync(occ_rec, s->dev.spheres + int64_t(s->dev.occluder) * 2, 32, hipMemcpyDeviceToHost, stream),
+            "hipMemcpyAsync(occluder record)");
   s->host_nodes.clear();  // the hot treelet downloads the refitted array when it next tunes
   sync_on_error.committed = true;
   RTG_HIP(hipStreamSynchronize(stream), "refit kernel");
+  if (s->dev.occluder >= 0) s->dev.occ = occluder_constants(occ_rec, s->dev.occluder);
   float ms0 = 0.0f, ms1 = 0.0f;
   RTG_HIP(hipEventElapsedTime(&ms0, s->ev0, s->ev1), "hipEventElapsedTime");
   RTG_HIP(hipEventElapsedTime(&ms1, s->ev2, s->ev3), "hipEventElapsedTime");

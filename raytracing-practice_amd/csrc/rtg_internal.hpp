@@ -170,6 +170,25 @@ struct DevCamera {
   int32_t defocus;  // defocus_angle > 0
 };
 
+// sphere_t forms c = |oc|^2 - r^2 in f64 for spheres of at least this radius (rtg_trav.hpp)
+constexpr float kSphereF64Radius = 16.0f;
+
+// The occluder's sphere test as scene constants (DESIGN.md §4 "occluder constants"): what sphere_t computes from
+// the record alone, computed once on the host with the same operations (rtg_api.cpp occluder_constants) and read
+// by the render kernels from their kernel arguments where the test runs. mode 0 (a moving occluder, or none):
+// the kernels run the general sphere_t on the record.
+struct DevOccluder {
+  double cd[3];    // the centre widened to double (the f64 chain's operand)
+  double r2;       // r * r, exact in double
+  float c[3];      // the centre at any time in [0, 1): c0 + time * (+-0)
+  float r;         // the radius (the record's, as the fp32 chain reads it)
+  int32_t index;   // DevScene::occluder
+  int32_t mode;    // 0: general path, 1: constants, |r| < kSphereF64Radius, 2: constants, the f64 chain
+  int32_t mat;     // the record's material
+  int32_t pad_;
+};
+static_assert(sizeof(DevOccluder) == 64 && alignof(DevOccluder) == 8, "DevOccluder is read as one 64-byte block");
+
 struct DevScene {
   const float4* nodes;
   const int32_t* refs;
@@ -218,6 +237,7 @@ struct DevScene {
   const float4* tris;
   const int2* tri_meta;
   int64_t num_tris;
+  DevOccluder occ;  // the occluder's test as constants (render kernels: read late from the kernel arguments)
 };
 
 // A render kernel picked for a plan (rtg_kernels.hip choose_kernel); fn == nullptr: none fits.

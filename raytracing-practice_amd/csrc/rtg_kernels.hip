@@ -340,17 +340,33 @@ __device__ __forceinline__ int lane_now() {
 }
 
 // Per-wave accumulators that outlive one tile.
+// `pixels` (the units a lane finished, the wave trace's third word) exists in the counting kernels only, as
+// the Counts do: in the product kernels it held a vector register across the whole render loop, the one the
+// 96-register builds were short of. RTG_WAVE_TRACE renders run the counting kernels.
+template <bool COUNT>
+struct TracePixels {
+  __device__ __forceinline__ void operator++() {}
+  __device__ __forceinline__ uint32_t get() const { return 0; }
+};
+template <>
+struct TracePixels<true> {
+  uint32_t n = 0;
+  __device__ __forceinline__ void operator++() { ++n; }
+  __device__ __forceinline__ uint32_t get() const { return n; }
+};
 template <bool COUNT>
 struct WaveStats {
-  uint32_t segs = 0, hits = 0, pixels = 0;
+  uint32_t segs = 0, hits = 0;
+  TracePixels<COUNT> pixels;
   Counts<COUNT> cnt;
   bool overflow = false, corrupt = false;
   uint64_t diag[16] = {};  // wave-uniform schedule diagnostics (COUNT only, rtg_render_stats::diag)
 };
 
+template <bool COUNT>
 __device__ __forceinline__ void trace_wave(const DevJob& J, uint64_t t0, uint32_t pixels, int lane,
                                            int slot, int tag) {
-  if (J.trace == nullptr) return;
+  if (!COUNT || J.trace == nullptr) return;
   const uint32_t wp = wave_sum(pixels);
   if (lane == 0) {
     unsigned long long* r = J.trace + static_cast<int64_t>(slot) * 4;
@@ -682,16 +698,16 @@ __device__ __forceinline__ void render_stream(const DevScene& S, const DevCamera
     }
     if (fresh || cont) {
       trav_begin<WIDE>(tr, S, ps.o, ps.d, ps.origin);
-      if (S.occluder >= 0) {  // the scene-spanning sphere kept out of the BVH (DevScene::occluder)
-        const float4* sp4 = S.spheres + static_cast<int64_t>(S.occluder) * S.sphere_f4;
-        if (COUNT) w.cnt.prim += 1;
-        const float th = sphere_t(sp4[0], sp4[1], ps.o, ps.d, tr.a, tr.inv_a, ps.time, kTMin, tr.tbest,
-                                  S.occluder == ps.origin);
-        if (th > 0.0f) {
-          tr.tbest = th;
-          tr.best = S.occluder;
-          if (GEOM != kGeomLds) tr.mat = ibits(sp4[1].w);  // (LDS schedule: tie rank -1 from trav_begin)
-        }
+      // the scene-spanning sphere kept out of the BVH (DevScene::occluder), its test from the scene's constants
+      // (occluder_t: read from the kernel arguments here, none of them held across the trip loop)
+      int32_t occ_ref = -1, occ_mat = -1;
+      const float th = occluder_t<COUNT>(S, ps.o, ps.d, tr.a, tr.inv_a, ps.time, tr.tbest, ps.origin, occ_ref, occ_mat,
+                                         w.corrupt);
+      if (COUNT && S.occluder >= 0) w.cnt.prim += 1;
+      if (th > 0.0f) {
+        tr.tbest = th;
+        tr.best = occ_ref;
+        if (GEOM != kGeomLds) tr.mat = occ_mat;  // (LDS schedule: tie rank -1 from trav_begin)
       }
     }
     fresh = false;
@@ -836,7 +852,7 @@ __global__ __launch_bounds__(256) void render_kernel(DevScene S, DevCamera C, De
     render_stream<LdsStack<STACK>, COUNT, WIDE, TEXF, kGeomGlobal, RING, PRIMS>(S, C, J, LdsStack<STACK>{lstk}, w, rtab);
   }
   flush_stats<COUNT>(J, w, lane_now());
-  trace_wave(J, t0, w.pixels, lane_now(), slot, (blockIdx.x << 8) | wave);
+  trace_wave<COUNT>(J, t0, w.pixels.get(), lane_now(), slot, (blockIdx.x << 8) | wave);
 }
 
 // Schedule 3's body: the whole scene in the workgroup's LDS (render_kernel_lds with GEOM = kGeomLds).
@@ -949,7 +965,7 @@ __device__ __forceinline__ void render_lds_scene(const DevScene& S, const DevCam
     render_stream<LdsStack<STACK>, COUNT, WIDE, TEXF, kGeomLds, RING, PRIMS>(L, C, J, LdsStack<STACK>{lstk}, w, rtab);
   }
   flush_stats<COUNT>(J, w, lane_now());
-  trace_wave(J, t0, w.pixels, lane_now(), blockIdx.x * wpb + wave, (blockIdx.x << 8) | wave);
+  trace_wave<COUNT>(J, t0, w.pixels.get(), lane_now(), blockIdx.x * wpb + wave, (blockIdx.x << 8) | wave);
 }
 
 // Schedule 3 (default when the geometry fits): persistent workgroups of WAVES waves, one per CU.
@@ -1003,7 +1019,7 @@ void render_kernel_lds(DevScene S, DevCamera C, DevJob J) {
                                                                                 rtab);
     }
     flush_stats<COUNT>(J, w, lane_now());
-    trace_wave(J, t0, w.pixels, lane_now(), blockIdx.x * wpb + wave, (blockIdx.x << 8) | wave);
+    trace_wave<COUNT>(J, t0, w.pixels.get(), lane_now(), blockIdx.x * wpb + wave, (blockIdx.x << 8) | wave);
   } else {
     render_lds_scene<STACK, SPILL, COUNT, WAVES, WIDE, TEXF, RING, PRIMS>(S, C, J, smem, kFill, wpb, t0, lane, wave,
                                                                           lstk, lstk16, rtab);

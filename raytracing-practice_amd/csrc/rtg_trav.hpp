@@ -177,9 +177,33 @@ __device__ __forceinline__ V3 random_unit_vector(uint64_t& s) {
 // `origin`: the ray starts on this sphere (its previous segment hit it): only the far root of a
 // ray entering the sphere counts (DESIGN.md §4 "origin rule"; fp32 puts the origin ~ulp(|p|) off
 // the surface, and a grazing ray's own root could pass tmin and trap a reflection inside).
-constexpr float kSphereF64Radius = 16.0f;
+// (kSphereF64Radius: rtg_internal.hpp, shared with the host's occluder constants)
 // a = d.d and inv_a = 1/a (correctly rounded) are per ray (Trav): the far root is q * inv_a and
 // only the near root c / q is a division.
+// The roots of a sphere test from its c, discriminant and half-b (the part of sphere_t after the two chains)
+template <bool INCL>
+__device__ __forceinline__ float sphere_roots(float c, float disc, float hb, float a, float inv_a, float tmin,
+                                              float tmax, bool origin) {
+  if (disc < 0.0f) return -1.0f;
+  const float sq = sqrtf(disc);
+  const float q = -(hb + copysignf(sq, hb));
+  // |q| < 2^-100 (a ray tangent at its own origin, q would otherwise have no lower bound) counts as a
+  // miss in the rtg-f32 spec (oracle/cpu_ref.c the same): div_rn is exact for every divisor left, and
+  // the guard is the compare the q == 0 test already made (ADVICE r02; div_rn_wide, which scaled tiny
+  // divisors instead, cost earth_perlin 4-6 % in register allocation, profiles/r03_c/ab_div_*)
+  if (fabsf(q) < 0x1p-100f || a == 0.0f) return -1.0f;
+  const float t0 = q * inv_a;
+  const float t1 = div_rn(c, q);
+  const float lo = fminf(t0, t1);
+  const float hi = fmaxf(t0, t1);
+  // roots inside (tmin, tmax), interval::surrounds (sphere.hpp:70); INCL: (tmin, tmax], so that the leaf test
+  // sees a root equal to the closest hit and applies the exact-t tie rule (DESIGN.md §4 "tie rule")
+  if (origin) return (hb < 0.0f && tmin < hi && (INCL ? hi <= tmax : hi < tmax)) ? hi : -1.0f;
+  if (tmin < lo && (INCL ? lo <= tmax : lo < tmax)) return lo;
+  if (tmin < hi && (INCL ? hi <= tmax : hi < tmax)) return hi;
+  return -1.0f;
+}
+
 template <bool INCL = false>
 __device__ __forceinline__ float sphere_t(float4 s0, float4 s1, V3 o, V3 d, float a, float inv_a, float time,
                                           float tmin, float tmax, bool origin) {
@@ -204,24 +228,7 @@ __device__ __forceinline__ float sphere_t(float4 s0, float4 s1, V3 o, V3 d, floa
     c = static_cast<float>(fma(-r, r, ox * ox + oy * oy + oz * oz));
     disc = fmaf(hb, hb, -(a * c));
   }
-  if (disc < 0.0f) return -1.0f;
-  const float sq = sqrtf(disc);
-  const float q = -(hb + copysignf(sq, hb));
-  // |q| < 2^-100 (a ray tangent at its own origin, q would otherwise have no lower bound) counts as a
-  // miss in the rtg-f32 spec (oracle/cpu_ref.c the same): div_rn is exact for every divisor left, and
-  // the guard is the compare the q == 0 test already made (ADVICE r02; div_rn_wide, which scaled tiny
-  // divisors instead, cost earth_perlin 4-6 % in register allocation, profiles/r03_c/ab_div_*)
-  if (fabsf(q) < 0x1p-100f || a == 0.0f) return -1.0f;
-  const float t0 = q * inv_a;
-  const float t1 = div_rn(c, q);
-  const float lo = fminf(t0, t1);
-  const float hi = fmaxf(t0, t1);
-  // roots inside (tmin, tmax), interval::surrounds (sphere.hpp:70); INCL: (tmin, tmax], so that the leaf test
-  // sees a root equal to the closest hit and applies the exact-t tie rule (DESIGN.md §4 "tie rule")
-  if (origin) return (hb < 0.0f && tmin < hi && (INCL ? hi <= tmax : hi < tmax)) ? hi : -1.0f;
-  if (tmin < lo && (INCL ? lo <= tmax : lo < tmax)) return lo;
-  if (tmin < hi && (INCL ? hi <= tmax : hi < tmax)) return hi;
-  return -1.0f;
+  return sphere_roots<INCL>(c, disc, hb, a, inv_a, tmin, tmax, origin);
 }
 
 // Scene classes a kernel is compiled for (PRIMS): bits 0-1 the primitives its leaf test and shading
@@ -320,6 +327,73 @@ __device__ __forceinline__ const int32_t* tile_order_late(const DevJob& J, bool&
   }
   return r;
 }
+// A wave-uniform kernel argument read where it is used: a volatile load through the constant address space is
+// a scalar load (s_load_dword..x16) issued at that point, so the value holds no SGPR from the kernel's start
+// across the trip loop (the compiler otherwise loads every argument once, first thing, and spills what does
+// not fit to VGPR lanes). Offsets come from offsetof / sizeof of the parameter structs only: every kernel that
+// runs render_stream takes (DevScene, DevCamera, DevJob) by value, each at its own alignment.
+typedef __attribute__((address_space(4))) const char karg_bytes;
+template <class T>
+__device__ __forceinline__ T karg(size_t off) {
+  karg_bytes* ka = (karg_bytes*)(__builtin_amdgcn_kernarg_segment_ptr());
+  return *reinterpret_cast<const volatile __attribute__((address_space(4))) T*>(ka + off);
+}
+typedef int karg_i4 __attribute__((ext_vector_type(4)));
+typedef int karg_i8 __attribute__((ext_vector_type(8)));
+typedef float karg_f4 __attribute__((ext_vector_type(4)));
+typedef float karg_f8 __attribute__((ext_vector_type(8)));
+typedef double karg_d4 __attribute__((ext_vector_type(4)));
+constexpr size_t kDevSceneKernarg = 0;
+constexpr size_t kDevCameraKernarg = align_up(sizeof(DevScene), alignof(DevCamera));
+static_assert(kDevJobKernarg == align_up(kDevCameraKernarg + sizeof(DevCamera), alignof(DevJob)),
+              "kernel arguments: DevScene, DevCamera, DevJob in that order");
+static_assert(offsetof(DevScene, occ) % 8 == 0 && offsetof(DevOccluder, cd) == 0 && offsetof(DevOccluder, r2) == 24 &&
+                  offsetof(DevOccluder, c) == 32 && offsetof(DevOccluder, r) == 44 &&
+                  offsetof(DevOccluder, index) == 48 && offsetof(DevOccluder, mode) == 52 &&
+                  offsetof(DevOccluder, mat) == 56,
+              "DevOccluder is read as {double4 cd + r2}, {float4 c + r}, {int4 index, mode, mat}");
+
+// The occluder (DevScene::occluder: the scene-spanning sphere kept out of the BVH) against one segment, as
+// sphere_t(record, o, d, ..., kTMin, tbest, origin == occluder) computes it. With DevOccluder::mode != 0 the record
+// loads, the centre at `time`, the widened centre, r * r and the radius branch are the host's constants (the same
+// operations on the same operands: DESIGN.md §4 "occluder constants"); every operation that involves the ray is
+// the one sphere_t runs, in its order. mode 0 runs sphere_t itself. Returns the root or -1; `ref`, `mat`: the occluder's sphere index and material.
+template <bool COUNT>
+__device__ __forceinline__ float occluder_t(const DevScene& S, V3 o, V3 d, float a, float inv_a, float time,
+                                            float tmax, int32_t origin, int32_t& ref, int32_t& mat, bool& corrupt) {
+  constexpr size_t kOcc = kDevSceneKernarg + offsetof(DevScene, occ);
+  const karg_i4 k = karg<karg_i4>(kOcc + offsetof(DevOccluder, index));  // index, mode, mat
+  if (COUNT && (k.x != S.occ.index || k.y != S.occ.mode)) corrupt = true;  // (the first argument is not the DevScene)
+  if (k.x < 0) return -1.0f;
+  ref = k.x;
+  if (k.y == 0) {
+    const float4* sp4 = S.spheres + static_cast<int64_t>(k.x) * S.sphere_f4;
+    const float4 s1 = sp4[1];
+    mat = ibits(s1.w);
+    return sphere_t(sp4[0], s1, o, d, a, inv_a, time, kTMin, tmax, k.x == origin);
+  }
+  mat = k.z;
+  const karg_f4 cr = karg<karg_f4>(kOcc + offsetof(DevOccluder, c));  // centre, radius
+  const V3 oc = sub(o, v3(cr.x, cr.y, cr.z));
+  const float hb = dot(oc, d);
+  float c, disc;
+  if (k.y == 1) {
+    c = fmaf(-cr.w, cr.w, dot(oc, oc));
+    const float s = hb * inv_a;
+    const V3 f = madd(-s, d, oc);
+    disc = a * fmaf(cr.w, cr.w, -dot(f, f));
+  } else {
+    const karg_d4 cd = karg<karg_d4>(kOcc + offsetof(DevOccluder, cd));  // widened centre, r * r
+    const double ox = static_cast<double>(o.x) - cd.x;
+    const double oy = static_cast<double>(o.y) - cd.y;
+    const double oz = static_cast<double>(o.z) - cd.z;
+    // sphere_t's fma(-r, r, sum): r * r is exact in f64, so its one rounding is this subtraction's
+    c = static_cast<float>((ox * ox + oy * oy + oz * oz) - cd.w);
+    disc = fmaf(hb, hb, -(a * c));
+  }
+  return sphere_roots<false>(c, disc, hb, a, inv_a, kTMin, tmax, k.x == origin);
+}
+
 // Cache-read schedules (Trav::mat holds the hit's material): the closest hit's rank is re-read from the
 // list ranks (a triangle's from its cold record), only on a tie (wave-uniform branch). Quads and triangles alike.
 template <bool TRIS = false>
