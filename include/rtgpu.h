@@ -414,6 +414,7 @@ typedef struct rtg_hit {
 #define RTG_QUERY_ANY 0x1    /* occlusion query: traversal ends at the first accepted hit */
 #define RTG_QUERY_DEVICE 0x2 /* rays / times / hits are device pointers on the scene's device */
 #define RTG_QUERY_ASYNC 0x4  /* needs DEVICE; returns once enqueued on `stream` */
+#define RTG_QUERY_SORT 0x8   /* trace the rays in the order of a coherence key (below); the answers do not move */
 /* bits 8-15: RTG_RENDER_SCHEDULE(n), the same diagnostic selector as rtg_render: 0 default, 3 scene in LDS,
  * 4 plain grid through the caches, 5 treelet; a schedule the scene cannot run is RTG_E_UNSUPPORTED */
 typedef struct rtg_query_desc {
@@ -428,9 +429,45 @@ typedef struct rtg_query_desc {
 typedef struct rtg_query_stats {
   uint64_t rays, hits;
   double kernel_ms;
-  uint64_t reserved_[5]; /* [0] schedule run, [1] workgroups, [2] waves per workgroup, [3] LDS bytes per workgroup */
+  uint64_t reserved_[5]; /* [0] schedule run, [1] workgroups, [2] waves per workgroup, [3] LDS bytes per workgroup,
+                            [4] RTG_QUERY_SORT: the sort kernels' share of kernel_ms in microseconds (else 0) */
 } rtg_query_stats;
 rtg_status rtg_intersect(rtg_scene* scene, const rtg_query_desc* q, rtg_query_stats* stats);
+
+/* ---- RTG_QUERY_SORT (additive in ABI 7): the batch's rays are bucketed on the device by a coherence key and the
+ * query's waves take their ray blocks in bucket order. The caller's arrays are untouched: hits[i] answers rays[i]
+ * and times[i] belongs to rays[i]; closest-hit answers are bit-identical to the unsorted query's (a ray's answer
+ * depends on the ray, the records and the tie ranks only), RTG_QUERY_ANY keeps its contract (the same hit / miss;
+ * the record may be another primitive's that really has a root). Valid with every other flag and every schedule;
+ * kernel_ms then covers the sort kernels and the traversal. The sort buffers are grow-only members of the scene.
+ *  - The key. A ray is a point in six axes: its origin, and its direction divided by |dx| + |dy| + |dz|. The
+ *    batch's box in those axes is taken over the rays the query traces (a non-finite ray, an origin of 1e30 or
+ *    more, dir == 0 or a direction whose L1 norm overflows stay out of it and get the largest key, 2^key_bits - 1,
+ *    so they end the order together). key_bits bits are split among the axes: each next bit goes to the axis
+ *    whose cells are widest, origin extents counted relative to the scene's extent (twice the largest
+ *    |coordinate| of its primitive boxes), direction extents relative to 2; an axis of zero extent gets none.
+ *    cell = min(int((x - lo) * cells / (hi - lo)), cells - 1) in fp32; the axes' cell bits are interleaved, origin
+ *    bits above direction bits. The sort is one unstable counting pass over the 2^key_bits buckets.
+ *  - rtg_ray_sort_keys_host computes the box, the bit shares and every ray's key of a host batch with the device's
+ *    arithmetic, bit for bit; it needs no GPU. `keys` (num_rays entries) and `layout` may each be NULL.
+ *  - rtg_query_last_order copies out the permutation (the ray index at each cursor position), the keys (by ray
+ *    index) and the layout of the scene's last sorted query, waiting for it first; `perm` and `keys` hold
+ *    `capacity` entries each (either may be NULL), *num_rays is 0 when the scene has not sorted yet or its last
+ *    sorted query had no rays. */
+#define RTG_QUERY_SORT_CHUNK 4096 /* a sort workgroup owns a contiguous chunk of at least this many rays */
+typedef struct rtg_sort_layout {
+  float lo[6], hi[6];  /* the batch box: origin x y z, direction x y z; meaningless when `empty` */
+  int32_t bits[6];     /* key bits of each axis */
+  int32_t key_bits;    /* their budget (the bucket count is 2^key_bits) */
+  int32_t empty;       /* 1: no ray of the batch is traced; every key is then 0 or the largest */
+  int32_t chunk;       /* rays per sort workgroup (rtg_query_last_order; 0 from rtg_ray_sort_keys_host) */
+  int32_t workgroups;  /* sort workgroups launched (likewise) */
+  double scene_extent; /* what the origin extents were counted against */
+} rtg_sort_layout;
+rtg_status rtg_ray_sort_keys_host(const rtg_ray* rays, int64_t num_rays, double scene_extent, uint16_t* keys,
+                                  rtg_sort_layout* layout);
+rtg_status rtg_query_last_order(rtg_scene* scene, int32_t* perm, uint16_t* keys, int64_t capacity, int64_t* num_rays,
+                                rtg_sort_layout* layout);
 
 /* ---- scene updates (ABI 7, additive): moving geometry without a rebuild ----
  * rtg_scene_update gives `count` primitives of a scene created with RTG_BVH_REFIT new coordinates and refits every

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "rtg_internal.hpp"
+#include "rtg_raysort.hpp"
 #include "rtg_refit.hpp"
 
 namespace rtg {
@@ -34,12 +35,12 @@ int lds_layout_treelet(DevScene* S, int stack, int waves, DevJob* J);
 bool dual_fits_registers(bool count, bool ring, bool verbose);
 hipError_t launch_resolve(const float* in, uint8_t* out, int64_t n_pixels, hipStream_t stream);
 // ray queries (rtg_query.hip)
-KernelChoice choose_query_kernel(const DevScene& S, int variant, bool any, bool spill);
+KernelChoice choose_query_kernel(const DevScene& S, int variant, bool any, bool spill, bool perm);
 int query_lds_layout(const DevScene& S, int waves, int entries, DevQuery* Q);
 int query_treelet_layout(DevScene* S, int waves, int entries, DevQuery* Q);
 hipError_t launch_query(const KernelChoice& k, const DevScene& S, const DevQuery& Q, int lds_bytes, int grid_blocks,
                         hipStream_t stream);
-hipError_t launch_origin_reach(const void* rays, uint32_t n, unsigned int* out, hipStream_t stream);
+hipError_t launch_origin_reach(const void* rays, uint32_t n, unsigned int* out, bool box, hipStream_t stream);
 }  // namespace rtg
 
 using namespace rtg;
@@ -66,6 +67,11 @@ constexpr int kSmallSceneWgs = 5;       // 4-wave persistent workgroups per CU f
 constexpr int64_t kRingAutoBytes = int64_t(32) << 30;
 constexpr int kNumCounters = 28;        // see DevJob::counters ([8..23] diagnostics, [24..25] tile ring, [26] stack spills,
                                         // [27] a device query batch's origin reach, float bits: rtg_intersect)
+// the counter allocations hold six more words after those: the twelve coded box words of a sorted device batch
+// (RTG_QUERY_SORT; rtg_query.hip origin_reach_kernel<true>), read back with the reach. Only sorted queries clear
+// and read them; renders and plain queries go on clearing and copying kNumCounters words.
+constexpr int kSortBoxCounters = 6;
+constexpr int kCounterWords = kNumCounters + kSortBoxCounters;
 // gfx950 allocates a workgroup's LDS in 1280-byte granules (160 KB = 128 of them): measured with the
 // dual launch, whose two workgroups stop sharing a CU exactly when the rounded sizes pass 160 KB
 constexpr int kLdsGranule = 1280;
@@ -1023,6 +1029,15 @@ struct rtg_scene {
   ScratchBuf scr_query;
   bool query_pending = false;
   hipStream_t query_stream = nullptr;
+  // RTG_QUERY_SORT: keys, permutation, count matrix and tile sums in one grow-only allocation (SortPlan), the event
+  // between the sort kernels and the traversal (created by the first sorted query), the extent origin boxes are
+  // counted against (twice HostScene::origin_bound as built; ensure_origin_reach does not move it), and what
+  // rtg_query_last_order reports
+  ScratchBuf scr_sort;
+  hipEvent_t ev_sort = nullptr;
+  double sort_extent = 0.0;
+  int64_t sort_last_n = 0;
+  rtg_sort_layout sort_last_layout{};
   // scene updates (RTG_BVH_REFIT; rtg_scene_update): one allocation of the slot of every input primitive (with
   // the kind bits of a leaf reference; host copy too), the triangles' vertex boxes, a parent and an arrival
   // word per node and the update kernel's two result words; two more events time the refit launches
@@ -1197,9 +1212,9 @@ rtg_status rtg_scene_create(const rtg_scene_desc* desc_in, int32_t device, rtg_s
     return cleanup(hip_fail(e, "hipStreamCreate"));
   if ((e = hipEventCreate(&s->ev0)) != hipSuccess || (e = hipEventCreate(&s->ev1)) != hipSuccess)
     return cleanup(hip_fail(e, "hipEventCreate"));
-  if ((e = dev_alloc(reinterpret_cast<void**>(&s->counters), kNumCounters * sizeof(unsigned long long))) != hipSuccess)
+  if ((e = dev_alloc(reinterpret_cast<void**>(&s->counters), kCounterWords * sizeof(unsigned long long))) != hipSuccess)
     return cleanup(hip_fail(e, "hipMalloc(counters)"));
-  if ((e = host_alloc(reinterpret_cast<void**>(&s->host_counters), kNumCounters * sizeof(unsigned long long))) != hipSuccess)
+  if ((e = host_alloc(reinterpret_cast<void**>(&s->host_counters), kCounterWords * sizeof(unsigned long long))) != hipSuccess)
     return cleanup(hip_fail(e, "hipHostMalloc(counters)"));
   char* base = static_cast<char*>(s->dmem);
   {
@@ -1373,6 +1388,7 @@ rtg_status rtg_scene_create(const rtg_scene_desc* desc_in, int32_t device, rtg_s
                          reinterpret_cast<const int32_t*>(hs.nodes.data()) + hs.nodes.size());
 
   s->origin_bound = hs.origin_bound;
+  s->sort_extent = 2.0 * hs.origin_bound;
   s->prim_index = std::move(hs.prim_index);
   s->info.device = device;
   s->info.bvh_mode = desc->bvh_mode | (refit ? RTG_BVH_REFIT : 0);
@@ -1413,7 +1429,8 @@ void rtg_scene_destroy(rtg_scene* s) {
   if (s->refit_mem) (void)hipFree(s->refit_mem);
   if (s->ev2) (void)hipEventDestroy(s->ev2);
   if (s->ev3) (void)hipEventDestroy(s->ev3);
-  for (ScratchBuf* b : {&s->scr_spill, &s->scr_trace, &s->scr_partial, &s->scr_query})
+  if (s->ev_sort) (void)hipEventDestroy(s->ev_sort);
+  for (ScratchBuf* b : {&s->scr_spill, &s->scr_trace, &s->scr_partial, &s->scr_query, &s->scr_sort})
     if (b->p) (void)hipFree(b->p);
   if (s->ev0) (void)hipEventDestroy(s->ev0);
   if (s->ev1) (void)hipEventDestroy(s->ev1);
@@ -2302,9 +2319,9 @@ rtg_status rtg_intersect(rtg_scene* s, const rtg_query_desc* q, rtg_query_stats*
   if (stats) *stats = rtg_query_stats{};
   if (q->num_rays < 0) return fail(RTG_E_INVALID, "num_rays is negative");
   const bool any = (q->flags & RTG_QUERY_ANY) != 0, dev = (q->flags & RTG_QUERY_DEVICE) != 0;
-  const bool async = (q->flags & RTG_QUERY_ASYNC) != 0;
+  const bool async = (q->flags & RTG_QUERY_ASYNC) != 0, sort = (q->flags & RTG_QUERY_SORT) != 0;
   if (async && !dev) return fail(RTG_E_INVALID, "RTG_QUERY_ASYNC requires RTG_QUERY_DEVICE");
-  if (q->flags & ~(RTG_QUERY_ANY | RTG_QUERY_DEVICE | RTG_QUERY_ASYNC | 0xff00))
+  if (q->flags & ~(RTG_QUERY_ANY | RTG_QUERY_DEVICE | RTG_QUERY_ASYNC | RTG_QUERY_SORT | 0xff00))
     return fail(RTG_E_INVALID, "unknown query flags");
   if (q->max_workgroups < 0) return fail(RTG_E_INVALID, "max_workgroups is negative");
   if (q->num_rays > 0 && (!q->rays || !q->hits)) return fail(RTG_E_INVALID, "null ray or hit array");
@@ -2336,7 +2353,7 @@ rtg_status rtg_intersect(rtg_scene* s, const rtg_query_desc* q, rtg_query_stats*
   KernelChoice kc;
   int lds_bytes = 0, wgs_per_cu = 1, waves = 4;
   if (variant == 0 || variant == 3) {
-    kc = choose_query_kernel(dscene, 3, any, spill);
+    kc = choose_query_kernel(dscene, 3, any, spill, sort);
     int best = 0;
     if (kc.fn) {
       const int wps = waves_per_simd(kc);
@@ -2357,14 +2374,14 @@ rtg_status rtg_intersect(rtg_scene* s, const rtg_query_desc* q, rtg_query_stats*
     }
   }
   if (variant == 5) {
-    kc = choose_query_kernel(dscene, 5, any, spill);
+    kc = choose_query_kernel(dscene, 5, any, spill, sort);
     if (!kc.fn) return fail(RTG_E_UNSUPPORTED, "the treelet query schedule needs a 4-wide BVH");
     waves = kLdsWaves;
     wgs_per_cu = 1;
     lds_bytes = query_treelet_layout(&dscene, waves, entries, &dq);
     if (lds_bytes < 0) return fail(RTG_E_UNSUPPORTED, "no LDS room for the treelet");
   } else if (variant == 4) {
-    kc = choose_query_kernel(dscene, 4, any, spill);
+    kc = choose_query_kernel(dscene, 4, any, spill, sort);
     waves = 4;
     // 16 KiB of static LDS stacks per workgroup
     wgs_per_cu = std::max(1, std::min(waves_per_simd(kc), kLdsPerCu / lds_alloc(4 * kLdsStack * 64 * 4)));
@@ -2376,7 +2393,10 @@ rtg_status rtg_intersect(rtg_scene* s, const rtg_query_desc* q, rtg_query_stats*
     stats->reserved_[2] = static_cast<uint64_t>(waves);
     stats->reserved_[3] = static_cast<uint64_t>(kc.dynamic_lds ? lds_bytes : 4 * kLdsStack * 64 * 4);
   }
-  if (q->num_rays == 0) return RTG_OK;  // nothing to launch
+  if (q->num_rays == 0) {  // nothing to launch (a sorted empty batch is the scene's last sorted query: no order)
+    if (sort) s->sort_last_n = 0;
+    return RTG_OK;
+  }
   const int64_t n = q->num_rays;
   int64_t grid = int64_t(s->num_cus) * wgs_per_cu;
   if (q->max_workgroups > 0) grid = std::min<int64_t>(grid, q->max_workgroups);
@@ -2410,21 +2430,36 @@ rtg_status rtg_intersect(rtg_scene* s, const rtg_query_desc* q, rtg_query_stats*
   }
   dq.prim_index = s->prim_index_dev;
   dq.counters = s->counters;
-  RTG_HIP(hipMemsetAsync(s->counters, 0, kNumCounters * sizeof(unsigned long long), stream), "hipMemsetAsync");
+  RTG_HIP(hipMemsetAsync(s->counters, 0, (sort ? kCounterWords : kNumCounters) * sizeof(unsigned long long), stream),
+          "hipMemsetAsync");
   double reach = 0.0;  // the largest |origin coordinate| (below 1e30) of the batch
+  // RTG_QUERY_SORT: the batch's six-axis box (rtg_raysort.hpp), from the same pass over the rays as the reach
+  float box_lo[kSortAxes] = {}, box_hi[kSortAxes] = {};
+  bool box_any = false;
   const size_t ray_bytes = static_cast<size_t>(n) * sizeof(rtg_ray), time_bytes = q->times ? static_cast<size_t>(n) * 4 : 0;
   if (dev) {
     dq.rays = reinterpret_cast<const float4*>(q->rays);
     dq.times = q->times;
     dq.hits = reinterpret_cast<float4*>(q->hits);
     unsigned int* word = reinterpret_cast<unsigned int*>(s->counters + 27);
-    RTG_HIP(launch_origin_reach(q->rays, dq.num_rays, word, stream), "origin reach kernel launch");
-    RTG_HIP(hipMemcpyAsync(s->host_counters + 27, s->counters + 27, 8, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(reach)");
+    RTG_HIP(launch_origin_reach(q->rays, dq.num_rays, word, sort, stream), "origin reach kernel launch");
+    RTG_HIP(hipMemcpyAsync(s->host_counters + 27, s->counters + 27, sort ? 8 + kSortBoxCounters * 8 : 8, hipMemcpyDeviceToHost,
+                           stream),
+            "hipMemcpyAsync(reach)");
     RTG_HIP(hipStreamSynchronize(stream), "origin reach kernel");
     float f;
     const uint32_t bits = static_cast<uint32_t>(s->host_counters[27]);
     std::memcpy(&f, &bits, 4);
     reach = f;
+    if (sort) {  // complemented lower ends, then upper ends; 0: no ray reached the box
+      uint32_t code[2 * kSortAxes];
+      std::memcpy(code, s->host_counters + 28, sizeof(code));
+      box_any = code[kSortAxes] != 0;
+      for (int a = 0; a < kSortAxes && box_any; ++a) {
+        box_lo[a] = sort_box_decode(~code[a]);
+        box_hi[a] = sort_box_decode(code[kSortAxes + a]);
+      }
+    }
   } else {
     // pinned staging (the scene's host_stage), then one DMA each way; rays | hits | times on the device
     const size_t stage_bytes = ray_bytes + time_bytes;  // >= the hits' bytes
@@ -2441,11 +2476,13 @@ rtg_status rtg_intersect(rtg_scene* s, const rtg_query_desc* q, rtg_query_stats*
     std::memcpy(stage, q->rays, ray_bytes);
     if (q->times) std::memcpy(stage + ray_bytes, q->times, time_bytes);
     float m = 0.0f;
-    for (int64_t k = 0; k < n; ++k)
+    for (int64_t k = 0; k < n; ++k) {
       for (int a = 0; a < 3; ++a) {
         const float v = std::fabs(q->rays[k].origin[a]);
         if (v < 1e30f && v > m) m = v;  // (a ray from farther out is a miss: rtg_query.hip kQueryOriginLimit)
       }
+      if (sort) sort_box_add(q->rays[k], &box_any, box_lo, box_hi);  // the same pass finds the batch box
+    }
     reach = m;
     char* dbase = static_cast<char*>(s->scr_query.p);
     RTG_HIP(hipMemcpyAsync(dbase, stage, ray_bytes, hipMemcpyHostToDevice, stream), "hipMemcpy(rays)");
@@ -2464,11 +2501,38 @@ rtg_status rtg_intersect(rtg_scene* s, const rtg_query_desc* q, rtg_query_stats*
     if (st != RTG_OK) return st;
     dq.spill = static_cast<int32_t*>(s->scr_spill.p);
   }
+  SortLayout sort_l{};
+  SortPlan sort_p;
+  if (sort) {  // the bit shares from the box (host), the buffers (grow-only), the record for rtg_query_last_order
+    sort_layout(box_lo, box_hi, !box_any, s->sort_extent, &sort_l);
+    st = grow(s->scr_sort, sort_plan(n, s->num_cus, nullptr, &sort_p), "hipMalloc(ray sort)");
+    if (st != RTG_OK) return st;
+    sort_plan(n, s->num_cus, s->scr_sort.p, &sort_p);
+    if (!s->ev_sort) RTG_HIP(hipEventCreate(&s->ev_sort), "hipEventCreate");
+    rtg_sort_layout& out = s->sort_last_layout;
+    out = rtg_sort_layout{};
+    for (int a = 0; a < kSortAxes; ++a) out.lo[a] = box_lo[a], out.hi[a] = box_hi[a], out.bits[a] = sort_l.bits[a];
+    out.key_bits = kSortKeyBits;
+    out.empty = box_any ? 0 : 1;
+    out.chunk = static_cast<int32_t>(sort_p.chunk);
+    out.workgroups = static_cast<int32_t>(sort_p.workgroups);
+    out.scene_extent = s->sort_extent;
+    s->sort_last_n = 0;  // until the kernels are enqueued
+    if (K.verbose)
+      std::fprintf(stderr, "[rtg] ray sort: %u workgroups x %u rays, key bits o %d %d %d d %d %d %d\n", sort_p.workgroups,
+                   sort_p.chunk, out.bits[0], out.bits[1], out.bits[2], out.bits[3], out.bits[4], out.bits[5]);
+  }
   if (K.verbose)
     std::fprintf(stderr, "[rtg] query schedule %d (%s): %lld workgroups of %d waves (%d per CU), %d B LDS, stack %d + %d\n",
                  variant, any ? "any" : "closest", static_cast<long long>(grid), waves, wgs_per_cu, lds_bytes,
                  dq.lds_stack, dq.spill_depth);
   RTG_HIP(hipEventRecord(s->ev0, stream), "hipEventRecord");
+  if (sort) {  // on the query's stream, inside [ev0, ev1]: kernel_ms covers the sort and the traversal
+    RTG_HIP(launch_ray_sort(sort_l, dq.rays, dq.num_rays, sort_p, stream), "ray sort kernel launch");
+    RTG_HIP(hipEventRecord(s->ev_sort, stream), "hipEventRecord");
+    dq.perm = sort_p.perm;
+    s->sort_last_n = n;
+  }
   RTG_HIP(launch_query(kc, dscene, dq, lds_bytes, static_cast<int>(grid), stream), "query kernel launch");
   RTG_HIP(hipEventRecord(s->ev1, stream), "hipEventRecord");
   RTG_HIP(hipMemcpyAsync(s->host_counters, s->counters, kNumCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost,
@@ -2489,11 +2553,58 @@ rtg_status rtg_intersect(rtg_scene* s, const rtg_query_desc* q, rtg_query_stats*
     stats->rays = s->host_counters[0];
     stats->hits = s->host_counters[3];
     stats->kernel_ms = ms;
+    if (sort) {
+      float sort_ms = 0.0f;
+      RTG_HIP(hipEventElapsedTime(&sort_ms, s->ev0, s->ev_sort), "hipEventElapsedTime");
+      stats->reserved_[4] = static_cast<uint64_t>(std::llround(static_cast<double>(sort_ms) * 1000.0));
+    }
   }
   if (st != RTG_OK) return st;
   if (s->host_counters[0] != static_cast<unsigned long long>(n))
     return fail(RTG_E_HIP, "the query answered " + std::to_string(s->host_counters[0]) + " of " + std::to_string(n) + " rays");
   if (!dev) std::memcpy(q->hits, s->host_stage, ray_bytes);
+  return RTG_OK;
+}
+
+rtg_status rtg_ray_sort_keys_host(const rtg_ray* rays, int64_t num_rays, double scene_extent, uint16_t* keys,
+                                  rtg_sort_layout* layout) {
+  if (num_rays < 0) return fail(RTG_E_INVALID, "num_rays is negative");
+  if (num_rays > 0 && !rays) return fail(RTG_E_INVALID, "null ray array");
+  float lo[kSortAxes] = {}, hi[kSortAxes] = {};
+  const bool any = sort_box_host(rays, num_rays, lo, hi);
+  SortLayout L;
+  sort_layout(lo, hi, !any, scene_extent, &L);
+  if (layout) {
+    *layout = rtg_sort_layout{};
+    for (int a = 0; a < kSortAxes; ++a) layout->lo[a] = lo[a], layout->hi[a] = hi[a], layout->bits[a] = L.bits[a];
+    layout->key_bits = kSortKeyBits;
+    layout->empty = any ? 0 : 1;
+    layout->scene_extent = scene_extent;
+  }
+  for (int64_t k = 0; keys && k < num_rays; ++k) {
+    const rtg_ray& r = rays[k];
+    float p[kSortAxes];
+    const bool ok = sort_point(r.origin[0], r.origin[1], r.origin[2], r.dir[0], r.dir[1], r.dir[2], p);
+    keys[k] = static_cast<uint16_t>(ok ? sort_key(L, p) : kSortInvalidKey);
+  }
+  return RTG_OK;
+}
+
+rtg_status rtg_query_last_order(rtg_scene* s, int32_t* perm, uint16_t* keys, int64_t capacity, int64_t* num_rays,
+                                rtg_sort_layout* layout) {
+  if (!s || !num_rays) return fail(RTG_E_INVALID, "null argument");
+  RTG_HIP(hipSetDevice(s->device), "hipSetDevice");
+  const rtg_status st = finish_query(s);
+  if (st != RTG_OK) return st;
+  const int64_t n = s->sort_last_n;
+  *num_rays = n;
+  if (layout) *layout = s->sort_last_layout;
+  if (n == 0) return RTG_OK;
+  if ((perm || keys) && capacity < n) return fail(RTG_E_INVALID, "capacity is below the last sorted query's ray count");
+  SortPlan P;
+  sort_plan(n, s->num_cus, s->scr_sort.p, &P);
+  if (perm) RTG_HIP(hipMemcpy(perm, P.perm, static_cast<size_t>(n) * 4, hipMemcpyDeviceToHost), "hipMemcpy(perm)");
+  if (keys) RTG_HIP(hipMemcpy(keys, P.keys, static_cast<size_t>(n) * 2, hipMemcpyDeviceToHost), "hipMemcpy(keys)");
   return RTG_OK;
 }
 

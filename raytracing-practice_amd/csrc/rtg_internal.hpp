@@ -380,6 +380,9 @@ struct DevQuery {
   int32_t leaf_batch;     // run a leaf trip once this many lanes wait at a leaf
   // persistent kernels: byte offsets in dynamic LDS (lds_tri_meta -1: cold records through the caches)
   int32_t lds_nodes, lds_stacks, lds_spheres, lds_quads, lds_tris, lds_tri_meta, lds_refs;
+  // RTG_QUERY_SORT: the ray index at each cursor position (rtg_raysort.hip), num_rays entries. Read by the PERM
+  // kernels only (null otherwise), and last in the struct: every other member lies where it lay without it
+  const uint32_t* perm;
 };
 
 }  // namespace rtg

@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <cstdint>
 
+#include "rtg_raysort.hpp"
 #include "rtg_trav.hpp"
 
 namespace rtg {
@@ -107,8 +108,10 @@ __device__ __forceinline__ void write_hit(const DevScene& S, const DevQuery& Q, 
   h[1] = h1;
 }
 
-// One wave answers rays from the launch's cursor until none are left.
-template <class Stk, int WIDE, int GEOM, int PRIMS, bool ANY>
+// One wave answers rays from the launch's cursor until none are left. PERM (RTG_QUERY_SORT): the cursor runs over
+// the sorted order, a cursor position's ray index comes from DevQuery::perm; the PERM = false instantiations never
+// read that member and are the kernels of the unsorted query as they were before the flag existed.
+template <class Stk, int WIDE, int GEOM, int PRIMS, bool ANY, bool PERM>
 __device__ __forceinline__ void query_stream(const DevScene& S, const DevQuery& Q, const Stk& stk, QueryWave& w) {
   constexpr int QRY = ANY ? kQueryAny : kQueryClosest;
   Trav tr = {};
@@ -140,7 +143,10 @@ __device__ __forceinline__ void query_stream(const DevScene& S, const DevQuery& 
       const uint32_t rank = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(want >> 32),
                                                       __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(want), 0u));
       if (idx == kNoRay && rank < take) {
-        idx = blk_next + rank;
+        if constexpr (PERM)
+          idx = Q.perm[blk_next + rank];
+        else
+          idx = blk_next + rank;
         ++w.rays;
         const float4* r = Q.rays + static_cast<uint64_t>(idx) * 2;
         const float4 r0 = r[0], r1 = r[1];
@@ -210,10 +216,10 @@ __device__ __forceinline__ void flush_query(const DevQuery& Q, QueryWave& w) {
   }
 }
 
-template <class Stk, int GEOM, int PRIMS, bool ANY>
+template <class Stk, int GEOM, int PRIMS, bool ANY, bool PERM>
 __device__ __forceinline__ void query_run(const DevScene& S, const DevQuery& Q, const Stk& stk) {
   QueryWave w;
-  query_stream<Stk, 4, GEOM, PRIMS, ANY>(S, Q, stk, w);
+  query_stream<Stk, 4, GEOM, PRIMS, ANY, PERM>(S, Q, stk, w);
   flush_query(Q, w);
 }
 
@@ -223,7 +229,7 @@ __device__ __forceinline__ void query_run(const DevScene& S, const DevQuery& Q, 
 // waves per SIMD) without scratch; the others are compiled for 6 (<= 80 registers; at 8 they spilled 16-92 B per
 // lane). The host packs a CU by the compiled register count (rtg_api.cpp rtg_intersect).
 constexpr int query_waves_per_simd(bool small) { return small ? 8 : 6; }
-template <bool SPILL, int PRIMS, bool ANY, int GEOM>
+template <bool SPILL, int PRIMS, bool ANY, int GEOM, bool PERM>
 __global__ __launch_bounds__(1024, query_waves_per_simd((PRIMS & kPrimsKind) == kPrimsTris && GEOM == kGeomLds))
 void query_kernel_lds(DevScene S, DevQuery Q) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -284,16 +290,16 @@ void query_kernel_lds(DevScene S, DevQuery Q) {
   if constexpr (SPILL) {
     const SpillStack<kLdsStack> stk{lstk, Q.spill + static_cast<int64_t>(slot) * Q.spill_depth * 64 + lane, Q.lds_stack,
                                     Q.lds_stack + Q.spill_depth};
-    query_run<SpillStack<kLdsStack>, GEOM, PRIMS, ANY>(L, Q, stk);
+    query_run<SpillStack<kLdsStack>, GEOM, PRIMS, ANY, PERM>(L, Q, stk);
   } else {
-    query_run<LdsStack<kLdsStack>, GEOM, PRIMS, ANY>(L, Q, LdsStack<kLdsStack>{lstk});
+    query_run<LdsStack<kLdsStack>, GEOM, PRIMS, ANY, PERM>(L, Q, LdsStack<kLdsStack>{lstk});
   }
 }
 
 // Schedule 4: 256-thread workgroups, the scene through the caches; 4-wide trees and the child-pair MEDIAN tree
 // (trav_begin<2>'s clamped reciprocals). One stack form: up to 16 entries per lane in LDS, deeper ones in the
 // spill area (empty where the tree needs none).
-template <int WIDE, bool ANY>
+template <int WIDE, bool ANY, bool PERM>
 __global__ __launch_bounds__(256, query_waves_per_simd(WIDE == 2)) void query_kernel(DevScene S, DevQuery Q) {
   __shared__ int32_t s_stack[4 * kLdsStack * 64];
   const int lane = threadIdx.x & 63;
@@ -303,58 +309,98 @@ __global__ __launch_bounds__(256, query_waves_per_simd(WIDE == 2)) void query_ke
                                   Q.spill + static_cast<int64_t>(slot) * Q.spill_depth * 64 + lane, Q.lds_stack,
                                   Q.lds_stack + Q.spill_depth};
   QueryWave w;
-  query_stream<SpillStack<kLdsStack>, WIDE, kGeomGlobal, kPrimsAny | kPrimsTriMix, ANY>(S, Q, stk, w);
+  query_stream<SpillStack<kLdsStack>, WIDE, kGeomGlobal, kPrimsAny | kPrimsTriMix, ANY, PERM>(S, Q, stk, w);
   flush_query(Q, w);
 }
 
 // The largest |origin coordinate| among the rays of a device-resident batch that can hit (reach3), as float bits (ordered
 // like the floats, being non-negative): rtg_intersect widens the culling margin for it before the query runs.
+// BOX (RTG_QUERY_SORT): the same pass also finds the batch's six-axis box (rtg_raysort.hpp sort_point), twelve
+// words after the reach's 64-bit word, coded so that every one is reduced by atomicMax from 0 (sort_box_code; the
+// lower ends complemented): per wave by shuffles, per workgroup through LDS, one atomic per word and workgroup.
+template <bool BOX>
 __global__ __launch_bounds__(256) void origin_reach_kernel(const float4* __restrict__ rays, uint32_t n,
                                                            unsigned int* __restrict__ out) {
   float m = 0.0f;
+  uint32_t box[BOX ? 2 * kSortAxes : 1] = {};
   for (uint64_t k = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; k < n;
        k += static_cast<uint64_t>(gridDim.x) * blockDim.x) {
     const float4 r = rays[k * 2];
     const float a = fmaxf(fmaxf(fabsf(r.x), fabsf(r.y)), fabsf(r.z));
     if (a < kQueryOriginLimit) m = fmaxf(m, a);
+    if constexpr (BOX) {
+      const float4 dr = rays[k * 2 + 1];
+      float p[kSortAxes];
+      if (sort_point(r.x, r.y, r.z, dr.x, dr.y, dr.z, p)) {
+#pragma unroll
+        for (int x = 0; x < kSortAxes; ++x) {
+          const uint32_t c = sort_box_code(p[x]);
+          box[x] = max(box[x], ~c);
+          box[kSortAxes + x] = max(box[kSortAxes + x], c);
+        }
+      }
+    }
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
   if ((threadIdx.x & 63) == 0 && m > 0.0f) atomicMax(out, __float_as_uint(m));
+  if constexpr (BOX) {
+    __shared__ uint32_t s_box[4][2 * kSortAxes];
+#pragma unroll
+    for (int x = 0; x < 2 * kSortAxes; ++x) {
+      uint32_t v = box[x];
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) v = max(v, static_cast<uint32_t>(__shfl_xor(static_cast<int>(v), off, 64)));
+      if ((threadIdx.x & 63) == 0) s_box[threadIdx.x >> 6][x] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * kSortAxes) {
+      const uint32_t v = max(max(s_box[0][threadIdx.x], s_box[1][threadIdx.x]), max(s_box[2][threadIdx.x], s_box[3][threadIdx.x]));
+      if (v != 0) atomicMax(out + 2 + threadIdx.x, v);
+    }
+  }
 }
 
 template <bool SPILL, int PRIMS, int GEOM>
-const void* lds_query_fn(bool any) {
-  return any ? reinterpret_cast<const void*>(&query_kernel_lds<SPILL, PRIMS, true, GEOM>)
-             : reinterpret_cast<const void*>(&query_kernel_lds<SPILL, PRIMS, false, GEOM>);
+const void* lds_query_fn(bool any, bool perm) {
+  if (perm)
+    return any ? reinterpret_cast<const void*>(&query_kernel_lds<SPILL, PRIMS, true, GEOM, true>)
+               : reinterpret_cast<const void*>(&query_kernel_lds<SPILL, PRIMS, false, GEOM, true>);
+  return any ? reinterpret_cast<const void*>(&query_kernel_lds<SPILL, PRIMS, true, GEOM, false>)
+             : reinterpret_cast<const void*>(&query_kernel_lds<SPILL, PRIMS, false, GEOM, false>);
+}
+template <int WIDE>
+const void* grid_query_fn(bool any, bool perm) {
+  if (perm)
+    return any ? reinterpret_cast<const void*>(&query_kernel<WIDE, true, true>)
+               : reinterpret_cast<const void*>(&query_kernel<WIDE, false, true>);
+  return any ? reinterpret_cast<const void*>(&query_kernel<WIDE, true, false>)
+             : reinterpret_cast<const void*>(&query_kernel<WIDE, false, false>);
 }
 
 }  // namespace
 
-// The family (16 kernels): {whole scene in LDS, treelet} x {mixed class: LdsStack, SpillStack; triangle-only
-// class: LdsStack (whole scene), SpillStack (treelet)} x {closest, any}; the plain grid for 4-wide and
-// child-pair trees x {closest, any}. variant: 3 LDS scene, 5 treelet, 4 plain grid.
-KernelChoice choose_query_kernel(const DevScene& S, int variant, bool any, bool spill) {
+// The family (16 kernels, and their 16 twins for RTG_QUERY_SORT: `perm`): {whole scene in LDS, treelet} x {mixed
+// class: LdsStack, SpillStack; triangle-only class: LdsStack (whole scene), SpillStack (treelet)} x {closest, any};
+// the plain grid for 4-wide and child-pair trees x {closest, any}. variant: 3 LDS scene, 5 treelet, 4 plain grid.
+KernelChoice choose_query_kernel(const DevScene& S, int variant, bool any, bool spill, bool perm) {
   constexpr int kMix = kPrimsAny | kPrimsTriMix;
   KernelChoice k;
   // the triangle-only class: records in reference order, no kind bit, and no sphere beside the tree (a mesh on a
   // scene-spanning sphere has a triangle-only tree too, but its winner may be the occluder: the mixed class)
   const bool tris_only = S.ref_mode == 3 && S.occluder < 0;
   if (variant == 3 && S.node_width == 4) {
-    k.fn = tris_only && !spill ? lds_query_fn<false, kPrimsTris, kGeomLds>(any)
-           : spill             ? lds_query_fn<true, kMix, kGeomLds>(any)
-                               : lds_query_fn<false, kMix, kGeomLds>(any);
+    k.fn = tris_only && !spill ? lds_query_fn<false, kPrimsTris, kGeomLds>(any, perm)
+           : spill             ? lds_query_fn<true, kMix, kGeomLds>(any, perm)
+                               : lds_query_fn<false, kMix, kGeomLds>(any, perm);
     k.dynamic_lds = true;
   } else if (variant == 5 && S.node_width == 4) {
-    k.fn = tris_only ? lds_query_fn<true, kPrimsTris, kGeomTreelet>(any)
-           : spill   ? lds_query_fn<true, kMix, kGeomTreelet>(any)
-                     : lds_query_fn<false, kMix, kGeomTreelet>(any);
+    k.fn = tris_only ? lds_query_fn<true, kPrimsTris, kGeomTreelet>(any, perm)
+           : spill   ? lds_query_fn<true, kMix, kGeomTreelet>(any, perm)
+                     : lds_query_fn<false, kMix, kGeomTreelet>(any, perm);
     k.dynamic_lds = true;
   } else if (variant == 4) {
-    if (S.node_width == 4)
-      k.fn = any ? reinterpret_cast<const void*>(&query_kernel<4, true>) : reinterpret_cast<const void*>(&query_kernel<4, false>);
-    else
-      k.fn = any ? reinterpret_cast<const void*>(&query_kernel<2, true>) : reinterpret_cast<const void*>(&query_kernel<2, false>);
+    k.fn = S.node_width == 4 ? grid_query_fn<4>(any, perm) : grid_query_fn<2>(any, perm);
     k.block = 256;
   }
   return k;
@@ -425,10 +471,13 @@ hipError_t launch_query(const KernelChoice& k, const DevScene& S, const DevQuery
   return hipLaunchKernel(k.fn, dim3(grid_blocks), dim3(k.block), args, k.dynamic_lds ? lds_bytes : 0, stream);
 }
 
-hipError_t launch_origin_reach(const void* rays, uint32_t n, unsigned int* out, hipStream_t stream) {
+hipError_t launch_origin_reach(const void* rays, uint32_t n, unsigned int* out, bool box, hipStream_t stream) {
   if (n == 0) return hipSuccess;
   const unsigned blocks = static_cast<unsigned>(std::min<uint64_t>((static_cast<uint64_t>(n) + 255) / 256, 1024));
-  hipLaunchKernelGGL(origin_reach_kernel, dim3(blocks), dim3(256), 0, stream, static_cast<const float4*>(rays), n, out);
+  if (box)
+    hipLaunchKernelGGL(origin_reach_kernel<true>, dim3(blocks), dim3(256), 0, stream, static_cast<const float4*>(rays), n, out);
+  else
+    hipLaunchKernelGGL(origin_reach_kernel<false>, dim3(blocks), dim3(256), 0, stream, static_cast<const float4*>(rays), n, out);
   return hipGetLastError();
 }
 

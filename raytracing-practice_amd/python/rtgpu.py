@@ -29,7 +29,8 @@ RTG_TEX_SOLID, RTG_TEX_CHECKER, RTG_TEX_IMAGE, RTG_TEX_NOISE = 1, 2, 3, 4
 RTG_BVH_MEDIAN, RTG_BVH_SAH, RTG_BVH_GPU = 0, 1, 3
 RTG_BVH_REFIT = 0x100  # or-ed into bvh_mode: the scene can be updated (DeviceScene.update)
 RTG_RENDER_OUT_DEVICE, RTG_RENDER_ASYNC, RTG_RENDER_COUNT = 0x1, 0x2, 0x4
-RTG_QUERY_ANY, RTG_QUERY_DEVICE, RTG_QUERY_ASYNC = 0x1, 0x2, 0x4
+RTG_QUERY_ANY, RTG_QUERY_DEVICE, RTG_QUERY_ASYNC, RTG_QUERY_SORT = 0x1, 0x2, 0x4, 0x8
+RTG_QUERY_SORT_CHUNK = 4096
 RTG_UPDATE_DEVICE = 0x1
 
 
@@ -149,6 +150,11 @@ class rtg_query_stats(C.Structure):
                 ("reserved_", C.c_uint64 * 5)]
 
 
+class rtg_sort_layout(C.Structure):
+    _fields_ = [("lo", C.c_float * 6), ("hi", C.c_float * 6), ("bits", C.c_int32 * 6), ("key_bits", C.c_int32),
+                ("empty", C.c_int32), ("chunk", C.c_int32), ("workgroups", C.c_int32), ("scene_extent", C.c_double)]
+
+
 class rtg_prim_update(C.Structure):
     _fields_ = [("p0", C.c_float * 3), ("radius", C.c_float), ("p1", C.c_float * 3), ("pad0_", C.c_float),
                 ("p2", C.c_float * 3), ("pad1_", C.c_float)]
@@ -190,7 +196,8 @@ RTG_SYMBOLS = ("rtg_abi_version", "rtg_last_error", "rtg_device_count", "rtg_cam
                "rtg_gather_rows", "rtg_deinterleave_rows", "rtg_render_frame", "rtg_render_plan",
                "rtg_shard_layout", "rtg_deinterleave_rows_host", "rtg_scene_prepare",
                "rtg_hot_treelet_order_host", "rtg_bvh_node_order",
-               "rtg_allocation_count", "rtg_intersect", "rtg_scene_update")
+               "rtg_allocation_count", "rtg_intersect", "rtg_scene_update",
+               "rtg_ray_sort_keys_host", "rtg_query_last_order")
 RTG_COMM_ID_BYTES = 128
 
 
@@ -277,12 +284,16 @@ class Library:
         L.rtg_allocation_count.argtypes = [_P(C.c_uint64), _P(C.c_uint64)]
         L.rtg_intersect.argtypes = [C.c_void_p, _P(rtg_query_desc), _P(rtg_query_stats)]
         L.rtg_scene_update.argtypes = [C.c_void_p, _P(rtg_update_desc), _P(rtg_update_stats)]
+        L.rtg_ray_sort_keys_host.argtypes = [C.c_void_p, C.c_int64, C.c_double, C.c_void_p, _P(rtg_sort_layout)]
+        L.rtg_query_last_order.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, _P(C.c_int64),
+                                           _P(rtg_sort_layout)]
         for name in ("rtg_device_count", "rtg_camera_resolve", "rtg_scene_create",
                      "rtg_scene_get_info", "rtg_render", "rtg_render_wait", "rtg_resolve_rgb8",
                      "rtg_bvh_build_host", "rtg_comm_create_local", "rtg_comm_unique_id",
                      "rtg_comm_create_rank", "rtg_comm_size", "rtg_gather_rows", "rtg_deinterleave_rows",
                      "rtg_render_frame", "rtg_render_plan", "rtg_shard_layout", "rtg_deinterleave_rows_host",
-                     "rtg_bvh_node_order", "rtg_allocation_count", "rtg_intersect", "rtg_scene_update"):
+                     "rtg_bvh_node_order", "rtg_allocation_count", "rtg_intersect", "rtg_scene_update",
+                     "rtg_ray_sort_keys_host", "rtg_query_last_order"):
             getattr(L, name).restype = C.c_int32
         if L.rtg_abi_version() != RTG_ABI_VERSION:
             raise RuntimeError("librtgpu ABI version mismatch")
@@ -327,6 +338,18 @@ class Library:
         n, b = C.c_uint64(0), C.c_uint64(0)
         self.check("rtg_allocation_count", self.lib.rtg_allocation_count(C.byref(n), C.byref(b)))
         return n.value, b.value
+
+    def ray_sort_keys_host(self, rays, scene_extent: float):
+        """rtg_ray_sort_keys_host: (keys, layout) of a numpy batch of RAY_DTYPE, the RTG_QUERY_SORT key of every ray
+        (uint16) and the batch box / bit shares they come from, computed on the host with the device's arithmetic."""
+        import numpy as np
+
+        rays = np.ascontiguousarray(rays, dtype=np.dtype(RAY_DTYPE))
+        keys = np.zeros(rays.shape[0], dtype=np.uint16)
+        layout = rtg_sort_layout()
+        self.check("rtg_ray_sort_keys_host", self.lib.rtg_ray_sort_keys_host(
+            rays.ctypes.data, rays.shape[0], scene_extent, keys.ctypes.data, C.byref(layout)))
+        return keys, layout
 
     def scene_create(self, desc: rtg_scene_desc, device: int = 0) -> "DeviceScene":
         h = C.c_void_p()
@@ -526,36 +549,56 @@ class DeviceScene:
                                                           C.byref(st)))
         return st
 
-    def intersect(self, rays, times=None, any_hit: bool = False, schedule: int = 0, max_workgroups: int = 0):
+    def intersect(self, rays, times=None, any_hit: bool = False, schedule: int = 0, max_workgroups: int = 0,
+                  sort: bool = False, hits=None):
         """Batched ray query (rtgpu.h rtg_intersect): `rays` a numpy array of RAY_DTYPE, `times` float32 per ray
-        or None; returns (hits, stats), hits a numpy array of HIT_DTYPE. any_hit: occlusion query."""
+        or None; returns (hits, stats), hits a numpy array of HIT_DTYPE. any_hit: occlusion query; sort:
+        RTG_QUERY_SORT, the rays are traced in the order of their coherence key (the answers do not move); hits: a
+        contiguous HIT_DTYPE array of the batch's length to fill instead of a new one."""
         import numpy as np
 
         rays = np.ascontiguousarray(rays, dtype=np.dtype(RAY_DTYPE))
-        hits = np.zeros(rays.shape[0], dtype=np.dtype(HIT_DTYPE))
+        if hits is None:
+            hits = np.zeros(rays.shape[0], dtype=np.dtype(HIT_DTYPE))
+        elif hits.dtype != np.dtype(HIT_DTYPE) or hits.shape != rays.shape or not hits.flags.c_contiguous:
+            raise ValueError("hits must be a contiguous HIT_DTYPE array with one record per ray")
         if times is not None:
             times = np.ascontiguousarray(times, dtype=np.float32)
             if times.shape != (rays.shape[0],):
                 raise ValueError("times must hold one float per ray")
         q = rtg_query_desc(rays.ctypes.data, times.ctypes.data if times is not None else None, rays.shape[0],
-                           hits.ctypes.data, (RTG_QUERY_ANY if any_hit else 0) | RTG_RENDER_SCHEDULE(schedule),
-                           max_workgroups, None)
+                           hits.ctypes.data, (RTG_QUERY_ANY if any_hit else 0) | (RTG_QUERY_SORT if sort else 0) |
+                           RTG_RENDER_SCHEDULE(schedule), max_workgroups, None)
         st = rtg_query_stats()
         self.L.check("rtg_intersect", self.L.lib.rtg_intersect(self.handle, C.byref(q), C.byref(st)))
         return hits, st
 
     def intersect_device(self, rays_ptr: int, num_rays: int, hits_ptr: int, times_ptr: int = 0,
                          stream_ptr: Optional[int] = None, any_hit: bool = False, schedule: int = 0,
-                         max_workgroups: int = 0, asynchronous: bool = False) -> rtg_query_stats:
+                         max_workgroups: int = 0, asynchronous: bool = False, sort: bool = False) -> rtg_query_stats:
         """The same on device memory of the scene's device (32-byte rtg_ray / rtg_hit records), on `stream_ptr`
         (hipStream_t); asynchronous: returns once enqueued."""
         flags = RTG_QUERY_DEVICE | (RTG_QUERY_ANY if any_hit else 0) | (RTG_QUERY_ASYNC if asynchronous else 0)
+        flags |= RTG_QUERY_SORT if sort else 0
         q = rtg_query_desc(C.c_void_p(rays_ptr), C.c_void_p(times_ptr) if times_ptr else None, num_rays,
                            C.c_void_p(hits_ptr), flags | RTG_RENDER_SCHEDULE(schedule), max_workgroups,
                            C.c_void_p(stream_ptr) if stream_ptr else None)
         st = rtg_query_stats()
         self.L.check("rtg_intersect", self.L.lib.rtg_intersect(self.handle, C.byref(q), C.byref(st)))
         return st
+
+    def query_last_order(self):
+        """rtg_query_last_order: (perm, keys, layout) of the scene's last sorted query: the ray index at each cursor
+        position (int32), every ray's key by ray index (uint16) and the rtg_sort_layout; empty arrays before one."""
+        import numpy as np
+
+        n, layout = C.c_int64(0), rtg_sort_layout()
+        call = self.L.lib.rtg_query_last_order
+        self.L.check("rtg_query_last_order", call(self.handle, None, None, 0, C.byref(n), C.byref(layout)))
+        perm, keys = np.zeros(n.value, dtype=np.int32), np.zeros(n.value, dtype=np.uint16)
+        self.L.check("rtg_query_last_order", call(self.handle, perm.ctypes.data, keys.ctypes.data, n.value, C.byref(n),
+                                                  C.byref(layout)))
+        return perm, keys, layout
 
     def update(self, indices, prims) -> rtg_update_stats:
         """rtg_scene_update from host memory (scenes created with RTG_BVH_REFIT): `prims` an (n, 12) float32 array or

@@ -13,6 +13,11 @@ if [ -n "${RES_REFIT:-}" ]; then
   src=rtg_refit.hip
   extra="-fPIC -fslp-vectorize -Xclang -target-feature -Xclang -packed-fp32-ops"
 fi
+# RES_SORT=1: the ray-sort kernels (rtg_raysort.hip)
+if [ -n "${RES_SORT:-}" ]; then
+  src=rtg_raysort.hip
+  extra="-fPIC -fslp-vectorize"
+fi
 /opt/rocm/bin/hipcc -std=c++17 -O3 --offload-arch=gfx950 -ffp-contract=off -fno-slp-vectorize -Iinclude \
   -Iraytracing-practice_amd/csrc ${RES_DEFS:-} $extra -c raytracing-practice_amd/csrc/$src -o /tmp/rtg_res.o \
   -Rpass-analysis=kernel-resource-usage 2>&1 |
