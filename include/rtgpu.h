@@ -113,6 +113,12 @@ typedef struct rtg_perlin {
  * rtg_scene_info.bvh_mode reports the mode with the bit; rtg_bvh_build_host ignores it. Scenes created without
  * it are exactly what they were: same device bytes, allocations and kernels. */
 #define RTG_BVH_REFIT 0x100
+/* May be or-ed into bvh_mode as well: the scene answers rtg_closest_point. It keeps one 48-byte edge record
+ * {Q, u.u}, {u, u.v}, {v, v.v} per triangle beside the plane-form record (which holds no vertices); a scene without
+ * triangles allocates nothing for the bit. Reported by rtg_scene_info.bvh_mode. A bit of rtg_scene_create only:
+ * rtg_bvh_build_host, which builds no records, goes on rejecting it (RTG_E_INVALID) like any bit but RTG_BVH_REFIT.
+ * Scenes created without it have exactly the device bytes, allocations and kernels they had. */
+#define RTG_BVH_NEAREST 0x200
 
 typedef struct rtg_scene_desc {
   uint32_t abi_version; /* RTG_ABI_VERSION (6 is still accepted: it has no tie_rank, read as NULL) */
@@ -526,6 +532,66 @@ typedef struct rtg_update_stats {
   uint64_t reserved_[4];
 } rtg_update_stats;
 rtg_status rtg_scene_update(rtg_scene* scene, const rtg_update_desc* u, rtg_update_stats* stats);
+
+/* ---- batched nearest-surface queries (additive in ABI 7; no reference counterpart) ----
+ * rtg_closest_point answers `num_points` points against a scene created with RTG_BVH_NEAREST: which primitive's
+ * surface is nearest to each, how far it is and where on it. A best-first walk of the scene's BVH, ordered and
+ * pruned by point-to-box distance (DESIGN.md §3 "Proximity queries", §4 "Proximity semantics").
+ *  - Distance: unsigned Euclidean distance from p to the primitive's surface. Sphere: | |p - c(time)| - |r| | with
+ *    c(time) = c0 + time (c1 - c0) as the ray test forms it, so a point inside a sphere measures to the shell. Quad:
+ *    the parallelogram Q + a u + b v, a and b in [0, 1]. Triangle: Q, Q + u, Q + v. `times` is one float per point,
+ *    or NULL for time 0.
+ *  - rtg_nearest: `prim` is the index into rtg_scene_desc.prims; on a miss it is -1, dist is -1 and the rest is 0.
+ *    `point` is the closest point; (u, v) are its (a, b) on a quad or triangle, get_sphere_uv of its outward unit
+ *    vector on a sphere (the functions rtg_hit's u, v go through); `side` is +1 when p is on the stored normal's
+ *    side of a quad or triangle (u x v) or outside a sphere, else -1. For p exactly at a sphere's centre `point`
+ *    is the centre plus |r| along +x.
+ *  - Radius: a primitive counts when dist <= max_dist; max_dist may be +inf. A non-finite coordinate, a
+ *    coordinate of 1e30 or more in magnitude, a NaN or negative max_dist, or a non-finite time is a miss for that
+ *    point, not an error.
+ *  - Determinism: the answer is a function of the point, the time, the primitive records and the input indices
+ *    only, never of the tree or the schedule. The squared distance is one fixed fp32 expression per primitive kind
+ *    (spheres of radius 16 or more take the difference in fp64); at bit-equal squared distance the lower input
+ *    index wins. Pruning is conservative: a subtree is skipped only when its fp32 box distance exceeds
+ *    best^2 (1 + 2^-19) plus a denormal guard, and node boxes are padded outward. The sphere kept out of the BVH is
+ *    tested first for every point.
+ *  - num_points == 0 is RTG_OK and launches nothing; num_points >= 2^31 is RTG_E_UNSUPPORTED. The descriptor (NULL,
+ *    negative count, unknown flags, NULL arrays with a count above 0) is checked before the scene is looked at, and
+ *    everything before any device work. A scene with triangles created without RTG_BVH_NEAREST is
+ *    RTG_E_UNSUPPORTED (scenes of spheres and quads answer without the bit).
+ *  - Blocking; not concurrent with renders of the same scene; waits for a ray query still in flight. Host batches
+ *    go through the scene's grow-only pinned and device staging: steady-state calls allocate nothing.
+ *  - rtg_scene_update on a RTG_BVH_REFIT | RTG_BVH_NEAREST scene rewrites the edge records of the triangles it
+ *    updates: the updated scene answers byte for byte as a fresh scene of the moved primitives. */
+typedef struct rtg_point {
+  float p[3];
+  float max_dist;
+} rtg_point; /* 16 B */
+typedef struct rtg_nearest {
+  float dist;
+  int32_t prim;
+  float u, v;
+  float point[3];
+  int32_t side;
+} rtg_nearest; /* 32 B */
+#define RTG_NEAREST_DEVICE 0x2 /* points / times / out are device pointers on the scene's device */
+/* bits 8-15: RTG_RENDER_SCHEDULE(n): 0 default (3 when the scene fits and the tree is 4-wide, else 4), 3 scene in
+ * LDS, 4 plain grid through the caches; 5, or a schedule the scene cannot run, is RTG_E_UNSUPPORTED */
+typedef struct rtg_nearest_desc {
+  const rtg_point* points;
+  const float* times; /* one per point, or NULL: 0 for every point */
+  int64_t num_points;
+  rtg_nearest* out;
+  int32_t flags;
+  int32_t max_workgroups; /* 0: library default */
+  void* stream;           /* hipStream_t, NULL: the scene's own stream */
+} rtg_nearest_desc;
+typedef struct rtg_nearest_stats {
+  uint64_t points, found;
+  double kernel_ms;
+  uint64_t reserved_[5]; /* [0] schedule run, [1] workgroups, [2] waves per workgroup, [3] LDS bytes per workgroup */
+} rtg_nearest_stats;
+rtg_status rtg_closest_point(rtg_scene* scene, const rtg_nearest_desc* q, rtg_nearest_stats* stats);
 
 /* ---- multi-GPU frames: row-interleaved shards, one RCCL gather over xGMI ----
  * Replaces the reference's single-device pixel loop of camera::render (camera.hpp:29-72) when the

@@ -41,6 +41,13 @@ int query_treelet_layout(DevScene* S, int waves, int entries, DevQuery* Q);
 hipError_t launch_query(const KernelChoice& k, const DevScene& S, const DevQuery& Q, int lds_bytes, int grid_blocks,
                         hipStream_t stream);
 hipError_t launch_origin_reach(const void* rays, uint32_t n, unsigned int* out, bool box, hipStream_t stream);
+// rtg_nearest.hip
+KernelChoice choose_nearest_kernel(const DevScene& S, int variant, bool spill);
+int nearest_lds_layout(const DevScene& S, int waves, int entries, DevNearest* Q);
+hipError_t launch_nearest(const KernelChoice& k, const DevScene& S, const DevNearest& Q, int lds_bytes, int grid_blocks,
+                          hipStream_t stream);
+hipError_t launch_update_edges(const int32_t* indices, const float4* prims, int64_t count, int64_t num_prims,
+                               const int32_t* slot_of, float4* edges, int64_t num_tris, hipStream_t stream);
 }  // namespace rtg
 
 using namespace rtg;
@@ -686,6 +693,13 @@ bool compile_scene(const rtg_scene_desc* d, HostScene* out, std::string* err) {
                                static_cast<float>(A.z),      static_cast<float>(-dot(A, Q)), static_cast<float>(B.x),
                                static_cast<float>(B.y),      static_cast<float>(B.z),      static_cast<float>(-dot(B, Q))};
         out->tris.insert(out->tris.end(), rec, rec + 12);
+        if (out->nearest) {  // the edge record: the vertices' floats and the three products, each rounded once
+          const float er[12] = {static_cast<float>(Q.x), static_cast<float>(Q.y), static_cast<float>(Q.z),
+                                static_cast<float>(dot(u, u)), static_cast<float>(u.x), static_cast<float>(u.y),
+                                static_cast<float>(u.z), static_cast<float>(dot(u, v)), static_cast<float>(v.x),
+                                static_cast<float>(v.y), static_cast<float>(v.z), static_cast<float>(dot(v, v))};
+          out->tri_edges.insert(out->tri_edges.end(), er, er + 12);
+        }
         out->tri_meta.push_back(p.material);
         out->tri_meta.push_back(static_cast<int32_t>(tie_rank(pid)));
         if (gpu_bvh || out->refit) {  // the device builder's (and a refit's) view of the triangle: its vertex box
@@ -1050,6 +1064,10 @@ struct rtg_scene {
   uint32_t* node_arrived = nullptr;
   unsigned long long* update_words = nullptr;
   hipEvent_t ev2 = nullptr, ev3 = nullptr;
+  // proximity queries (RTG_BVH_NEAREST; rtg_closest_point): the triangles' edge records, an allocation of their
+  // own (null in a scene without triangles or without the bit)
+  bool nearest = false;
+  float4* tri_edges = nullptr;
   // deferred (async) render state
   bool pending = false;
   hipStream_t pending_stream = nullptr;
@@ -1091,8 +1109,8 @@ rtg_status rtg_bvh_build_host(const rtg_scene_desc* desc, rtg_bvh_node_host* nod
     return fail(RTG_E_INVALID, "malformed primitive array");
   Bvh bvh;
   std::string err;
-  rtg_scene_desc plain = *desc;  // RTG_BVH_REFIT changes nothing of the tree
-  plain.bvh_mode &= ~RTG_BVH_REFIT;
+  rtg_scene_desc plain = *desc;  // RTG_BVH_REFIT changes nothing of the tree (RTG_BVH_NEAREST is a creation bit only:
+  plain.bvh_mode &= ~RTG_BVH_REFIT;  // here it is an unknown bit, as tests/test_update.py pins for 0x200)
   if (!build_bvh(&plain, &bvh, &err)) return fail(RTG_E_INVALID, err);
   if (num_nodes) *num_nodes = static_cast<int64_t>(bvh.nodes.size());
   if (num_refs) *num_refs = static_cast<int64_t>(bvh.refs.size());
@@ -1146,11 +1164,13 @@ rtg_status rtg_scene_create(const rtg_scene_desc* desc_in, int32_t device, rtg_s
   const rtg_scene_desc* desc = &desc_v;
   // RTG_BVH_REFIT rides on the mode: the builders see the plain mode (any other unknown bit stays invalid there)
   const bool refit = (desc_v.bvh_mode & RTG_BVH_REFIT) != 0;
-  desc_v.bvh_mode &= ~RTG_BVH_REFIT;
+  const bool nearest = (desc_v.bvh_mode & RTG_BVH_NEAREST) != 0;  // as RTG_BVH_REFIT: the builders never see it
+  desc_v.bvh_mode &= ~(RTG_BVH_REFIT | RTG_BVH_NEAREST);
   // validate + compile first (host only), so malformed scenes report RTG_E_INVALID anywhere
   const auto t0 = std::chrono::steady_clock::now();
   HostScene hs;
   hs.refit = refit;
+  hs.nearest = nearest;
   std::string err;
   if (!compile_scene(desc, &hs, &err)) return fail(RTG_E_INVALID, err);
   if (hs.stack_need > kMaxStackNeed)
@@ -1288,6 +1308,17 @@ rtg_status rtg_scene_create(const rtg_scene_desc* desc_in, int32_t device, rtg_s
       return cleanup(hip_fail(e, "hipEventCreate"));
     s->refit = true;
   }
+  // RTG_BVH_NEAREST: the triangles' edge records (a scene without triangles allocates nothing for the bit)
+  size_t edge_bytes = 0;
+  s->nearest = nearest;
+  if (nearest && !hs.tri_edges.empty()) {
+    edge_bytes = hs.tri_edges.size() * 4;
+    if ((e = dev_alloc(reinterpret_cast<void**>(&s->tri_edges), edge_bytes)) != hipSuccess)
+      return cleanup(hip_fail(e, "hipMalloc(edge records)"));
+    e = hipMemcpyAsync(s->tri_edges, hs.tri_edges.data(), edge_bytes, hipMemcpyHostToDevice, s->own_stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->own_stream);
+    if (e != hipSuccess) return cleanup(hip_fail(e, "hipMemcpy(edge records)"));
+  }
   const auto t2 = std::chrono::steady_clock::now();
   double gpu_build_ms = 0.0;
   const int64_t nrefs = static_cast<int64_t>(hs.refs.size());
@@ -1391,13 +1422,13 @@ rtg_status rtg_scene_create(const rtg_scene_desc* desc_in, int32_t device, rtg_s
   s->sort_extent = 2.0 * hs.origin_bound;
   s->prim_index = std::move(hs.prim_index);
   s->info.device = device;
-  s->info.bvh_mode = desc->bvh_mode | (refit ? RTG_BVH_REFIT : 0);
+  s->info.bvh_mode = desc->bvh_mode | (refit ? RTG_BVH_REFIT : 0) | (nearest ? RTG_BVH_NEAREST : 0);
   s->info.num_prims = hs.num_prims;
   s->info.num_nodes = hs.num_nodes;
   s->info.bvh_depth = hs.depth;
   s->info.stack_depth = hs.stack_need;
   s->stack_need = hs.stack_need;
-  s->info.device_bytes = static_cast<int64_t>(total + refit_bytes);
+  s->info.device_bytes = static_cast<int64_t>(total + refit_bytes + edge_bytes);
   s->info.build_ms = std::chrono::duration<double, std::milli>(t1 - t0).count() + gpu_build_ms;
   s->info.upload_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
   s->info.bvh_ms = hs.bvh_ms + gpu_build_ms;
@@ -1427,6 +1458,7 @@ void rtg_scene_destroy(rtg_scene* s) {
   if (s->query_pending && s->query_stream) (void)hipStreamSynchronize(s->query_stream);
   if (s->prim_index_dev) (void)hipFree(s->prim_index_dev);
   if (s->refit_mem) (void)hipFree(s->refit_mem);
+  if (s->tri_edges) (void)hipFree(s->tri_edges);
   if (s->ev2) (void)hipEventDestroy(s->ev2);
   if (s->ev3) (void)hipEventDestroy(s->ev3);
   if (s->ev_sort) (void)hipEventDestroy(s->ev_sort);
@@ -2608,6 +2640,176 @@ rtg_status rtg_query_last_order(rtg_scene* s, int32_t* perm, uint16_t* keys, int
   return RTG_OK;
 }
 
+rtg_status rtg_closest_point(rtg_scene* s, const rtg_nearest_desc* q, rtg_nearest_stats* stats) {
+  // the descriptor first, then the scene (rtgpu.h): nothing of the scene is read before these checks
+  if (!q) return fail(RTG_E_INVALID, "null query descriptor");
+  if (stats) *stats = rtg_nearest_stats{};
+  if (q->num_points < 0) return fail(RTG_E_INVALID, "num_points is negative");
+  if (q->flags & ~(RTG_NEAREST_DEVICE | 0xff00)) return fail(RTG_E_INVALID, "unknown query flags");
+  if (q->max_workgroups < 0) return fail(RTG_E_INVALID, "max_workgroups is negative");
+  if (q->num_points > 0 && (!q->points || !q->out)) return fail(RTG_E_INVALID, "null point or result array");
+  if (q->num_points >= (int64_t(1) << 31))
+    return fail(RTG_E_UNSUPPORTED, "num_points must be below 2^31 (split the batch)");
+  if (!s) return fail(RTG_E_INVALID, "null scene");
+  if (s->pending) return fail(RTG_E_INVALID, "a previous async render was not waited for");
+  const bool dev = (q->flags & RTG_NEAREST_DEVICE) != 0;
+  int variant = (q->flags >> 8) & 0xff;
+  if (variant == 5) return fail(RTG_E_UNSUPPORTED, "proximity queries have no treelet schedule");
+  if (variant != 0 && variant != 3 && variant != 4) return fail(RTG_E_INVALID, "unknown query schedule");
+  if (s->dev.num_tris > 0 && !s->tri_edges)
+    return fail(RTG_E_UNSUPPORTED, "the scene has triangles and was created without RTG_BVH_NEAREST");
+  if (s->prim_index.empty() && s->dev.num_refs + (s->dev.occluder >= 0 ? 1 : 0) > 0)
+    return fail(RTG_E_UNSUPPORTED, "proximity queries need fewer than 2^31 primitives");
+  RTG_HIP(hipSetDevice(s->device), "hipSetDevice");
+  rtg_status st = finish_query(s);
+  if (st != RTG_OK) return st;
+
+  // ---- the launch plan, from this kernel family's own LDS need (two stacks; edge records, no plane forms)
+  const Knobs& K = s->knobs;
+  const int need = std::max(1, s->stack_need);
+  int entries = K.stack_lds_entries > 0 ? std::min(kLdsStack, K.stack_lds_entries) : kLdsStack;
+  const bool spill = need > entries;
+  if (!spill) entries = kLdsStack;  // the LdsStack kernel's layout
+  DevScene dscene = s->dev;
+  dscene.node_visits = nullptr;
+  DevNearest dn{};
+  auto waves_per_simd = [](const KernelChoice& k) {  // 512 registers per lane, granule 8
+    const KernelResources r = kernel_resources(k.fn);
+    return r.ok && r.vgprs > 0 ? std::max(1, std::min(8, 512 / ((r.vgprs + 7) / 8 * 8))) : 4;
+  };
+  KernelChoice kc;
+  int lds_bytes = 0, wgs_per_cu = 1, waves = 4;
+  if (variant == 0 || variant == 3) {
+    kc = choose_nearest_kernel(dscene, 3, spill);
+    int best = 0;
+    if (kc.fn) {
+      const int wps = waves_per_simd(kc);
+      for (const int w : {16, 8, 4}) {  // the shape with the most resident waves; ties to the larger workgroup
+        const int b = nearest_lds_layout(dscene, w, entries, nullptr);
+        if (b < 0) continue;
+        const int g = std::min(kLdsPerCu / lds_alloc(b), wps * 4 / w);
+        if (g * w > best) best = g * w, waves = w, wgs_per_cu = g;
+      }
+    }
+    if (best > 0) {
+      variant = 3;
+      lds_bytes = nearest_lds_layout(dscene, waves, entries, &dn);
+    } else if (variant == 3) {
+      return fail(RTG_E_UNSUPPORTED, "scene does not fit the LDS proximity schedule (or its tree is not 4-wide)");
+    } else {
+      variant = 4;
+    }
+  }
+  constexpr int kGridLds = 4 * 2 * kLdsStack * 64 * 4;  // schedule 4: 32 KiB of static LDS stacks per workgroup
+  if (variant == 4) {
+    kc = choose_nearest_kernel(dscene, 4, spill);
+    waves = 4;
+    wgs_per_cu = std::max(1, std::min(waves_per_simd(kc), kLdsPerCu / lds_alloc(kGridLds)));
+  }
+  if (!kc.fn) return fail(RTG_E_UNSUPPORTED, "no proximity kernel fits this scene");
+  kc.block = waves * 64;
+  if (stats) {
+    stats->reserved_[0] = static_cast<uint64_t>(variant);
+    stats->reserved_[2] = static_cast<uint64_t>(waves);
+    stats->reserved_[3] = static_cast<uint64_t>(kc.dynamic_lds ? lds_bytes : kGridLds);
+  }
+  if (q->num_points == 0) return RTG_OK;  // nothing to launch
+  const int64_t n = q->num_points;
+  int64_t grid = int64_t(s->num_cus) * wgs_per_cu;
+  if (q->max_workgroups > 0) grid = std::min<int64_t>(grid, q->max_workgroups);
+  grid = std::max<int64_t>(1, std::min(grid, (n + kc.block - 1) / kc.block));  // what the points can fill
+  if (stats) stats->reserved_[1] = static_cast<uint64_t>(grid);
+  dn.num_points = static_cast<uint32_t>(n);
+  dn.lds_stack = entries;
+  dn.spill_depth = std::max(0, need - entries);
+  dn.refill_batch = K.query_refill;
+  dn.block = static_cast<int32_t>(std::max<int64_t>(64, std::min<int64_t>(512, n / (grid * waves * 8) / 64 * 64)));
+  dn.leaf_batch = s->dev.num_nodes <= kSmallBvhNodes ? kSmallBvhLeafBatch : kDefaultLeafBatch;  // the ray query's
+  dn.edges = s->tri_edges;
+
+  hipStream_t stream = q->stream ? static_cast<hipStream_t>(q->stream) : s->own_stream;
+  SyncOnError sync_on_error;
+  sync_on_error.stream = stream;
+  auto grow = [](ScratchBuf& b, size_t bytes, const char* what) -> rtg_status {
+    if (b.p && b.bytes >= bytes) return RTG_OK;
+    if (b.p) RTG_HIP(hipFree(b.p), "hipFree(scratch)");  // device-synchronous: nothing still reads it
+    b.p = nullptr;
+    b.bytes = 0;
+    RTG_HIP(dev_alloc(&b.p, std::max<size_t>(bytes, 256)), what);
+    b.bytes = bytes;
+    return RTG_OK;
+  };
+  if (!s->prim_index_dev && !s->prim_index.empty()) {  // the scene's first query of either kind
+    RTG_HIP(dev_alloc(reinterpret_cast<void**>(&s->prim_index_dev), s->prim_index.size() * 4), "hipMalloc(prim index)");
+    RTG_HIP(hipMemcpy(s->prim_index_dev, s->prim_index.data(), s->prim_index.size() * 4, hipMemcpyHostToDevice),
+            "hipMemcpy(prim index)");
+  }
+  dn.prim_index = s->prim_index_dev;
+  dn.counters = s->counters;
+  const size_t point_bytes = static_cast<size_t>(n) * sizeof(rtg_point), out_bytes = static_cast<size_t>(n) * sizeof(rtg_nearest);
+  const size_t time_bytes = q->times ? static_cast<size_t>(n) * 4 : 0;
+  if (dev) {
+    dn.points = reinterpret_cast<const float4*>(q->points);
+    dn.times = q->times;
+    dn.out = reinterpret_cast<float4*>(q->out);
+  } else {
+    // pinned staging (the scene's host_stage), then one DMA each way; results | points | times on the device
+    const size_t stage_bytes = std::max(out_bytes, point_bytes + time_bytes);
+    if (s->host_stage_bytes < stage_bytes) {
+      if (s->host_stage) RTG_HIP(hipHostFree(s->host_stage), "hipHostFree(stage)");
+      s->host_stage = nullptr;
+      s->host_stage_bytes = 0;
+      RTG_HIP(host_alloc(&s->host_stage, stage_bytes), "hipHostMalloc(stage)");
+      s->host_stage_bytes = stage_bytes;
+    }
+    st = grow(s->scr_query, out_bytes + point_bytes + static_cast<size_t>(n) * 4, "hipMalloc(query staging)");
+    if (st != RTG_OK) return st;
+    char* stage = static_cast<char*>(s->host_stage);
+    std::memcpy(stage, q->points, point_bytes);
+    if (q->times) std::memcpy(stage + point_bytes, q->times, time_bytes);
+    char* dbase = static_cast<char*>(s->scr_query.p);
+    RTG_HIP(hipMemcpyAsync(dbase + out_bytes, stage, point_bytes + time_bytes, hipMemcpyHostToDevice, stream),
+            "hipMemcpy(points)");
+    dn.out = reinterpret_cast<float4*>(dbase);
+    dn.points = reinterpret_cast<const float4*>(dbase + out_bytes);
+    dn.times = q->times ? reinterpret_cast<const float*>(dbase + out_bytes + point_bytes) : nullptr;
+  }
+  dn.spill = nullptr;
+  if (dn.spill_depth > 0) {  // the render's spill area, two stacks deep (queries and renders of a scene never overlap)
+    st = grow(s->scr_spill, static_cast<size_t>(grid) * waves * 64 * dn.spill_depth * 2 * sizeof(int32_t), "hipMalloc(stack spill)");
+    if (st != RTG_OK) return st;
+    dn.spill = static_cast<int32_t*>(s->scr_spill.p);
+  }
+  if (K.verbose)
+    std::fprintf(stderr, "[rtg] proximity schedule %d: %lld workgroups of %d waves (%d per CU), %d B LDS, stacks %d + %d\n",
+                 variant, static_cast<long long>(grid), waves, wgs_per_cu, lds_bytes, dn.lds_stack, dn.spill_depth);
+  RTG_HIP(hipMemsetAsync(s->counters, 0, kNumCounters * sizeof(unsigned long long), stream), "hipMemsetAsync");
+  RTG_HIP(hipEventRecord(s->ev0, stream), "hipEventRecord");
+  RTG_HIP(launch_nearest(kc, dscene, dn, lds_bytes, static_cast<int>(grid), stream), "proximity kernel launch");
+  RTG_HIP(hipEventRecord(s->ev1, stream), "hipEventRecord");
+  RTG_HIP(hipMemcpyAsync(s->host_counters, s->counters, kNumCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                         stream),
+          "hipMemcpyAsync(counters)");
+  if (!dev) RTG_HIP(hipMemcpyAsync(s->host_stage, dn.out, out_bytes, hipMemcpyDeviceToHost, stream), "hipMemcpy(results)");
+  sync_on_error.committed = true;
+  RTG_HIP(hipStreamSynchronize(stream), "proximity kernel");
+  const unsigned long long* c = s->host_counters;
+  float ms = 0.0f;
+  RTG_HIP(hipEventElapsedTime(&ms, s->ev0, s->ev1), "hipEventElapsedTime");
+  if (stats) {
+    stats->points = c[0];
+    stats->found = c[3];
+    stats->kernel_ms = ms;
+  }
+  if (c[4] != 0)
+    return fail(RTG_E_UNSUPPORTED, "BVH traversal stack overflow in " + std::to_string(c[4]) + " waves (proximity query)");
+  if (c[5] != 0) return fail(RTG_E_INVALID, "corrupt BVH child code met during a proximity query's traversal");
+  if (c[0] != static_cast<unsigned long long>(n))
+    return fail(RTG_E_HIP, "the query answered " + std::to_string(c[0]) + " of " + std::to_string(n) + " points");
+  if (!dev) std::memcpy(q->out, s->host_stage, out_bytes);
+  return RTG_OK;
+}
+
 rtg_status rtg_scene_update(rtg_scene* s, const rtg_update_desc* u, rtg_update_stats* stats) {
   // the descriptor first, then the scene (rtgpu.h); everything before any device work
   if (!u) return fail(RTG_E_INVALID, "null update descriptor");
@@ -2696,6 +2898,9 @@ rtg_status rtg_scene_update(rtg_scene* s, const rtg_update_desc* u, rtg_update_s
   RTG_HIP(hipMemsetAsync(s->update_words, 0, 16, stream), "hipMemsetAsync");
   RTG_HIP(hipEventRecord(s->ev0, stream), "hipEventRecord");
   RTG_HIP(launch_update_records(ua, stream), "update kernel launch");
+  if (s->tri_edges)  // RTG_BVH_NEAREST: the updated triangles' edge records, by the record kernel's acceptance rule
+    RTG_HIP(launch_update_edges(ua.indices, ua.prims, n, np, s->slot_of_dev, s->tri_edges, s->dev.num_tris, stream),
+            "edge record kernel launch");
   RTG_HIP(hipEventRecord(s->ev1, stream), "hipEventRecord");
   uint64_t invalid = 0;
   if (dev) {  // the batch's reach and rejections: one read-back, the wait rtg_intersect takes for its origin reach

@@ -46,6 +46,10 @@ struct HostScene {
   // plane-form records do not hold the vertices); uploaded for the device build, then dropped, or kept for refits
   std::vector<float> tri_boxes;
   bool refit = false;  // in: RTG_BVH_REFIT (set before compile_scene)
+  // RTG_BVH_NEAREST only: each triangle slot's edge record {Q.xyz, u.u}, {u.xyz, u.v}, {v.xyz, v.v} (12 floats; the
+  // products in fp64 from the descriptor's doubles, rounded once): what rtg_closest_point's triangle test reads
+  std::vector<float> tri_edges;
+  bool nearest = false;  // in: RTG_BVH_NEAREST (set before compile_scene)
   std::vector<float> materials;  // 8 floats per material
   std::vector<float> textures;   // 8 floats per texture
   std::vector<int32_t> image_hdr;  // 4 ints per image
@@ -383,6 +387,27 @@ struct DevQuery {
   // RTG_QUERY_SORT: the ray index at each cursor position (rtg_raysort.hip), num_rays entries. Read by the PERM
   // kernels only (null otherwise), and last in the struct: every other member lies where it lay without it
   const uint32_t* perm;
+};
+
+// One proximity-query launch (rtg_closest_point; kernels in rtg_nearest.hip), passed by value after the DevScene.
+struct DevNearest {
+  const float4* points;  // one per point: {p, max_dist}
+  const float* times;    // one per point, or null: 0 for every point
+  float4* out;           // 2 per point: {dist, prim, u, v}, {point, side}
+  // [0] points answered, [3] found, [4] stack overflow, [5] bad BVH code, [6] the point cursor (the scene's counters)
+  unsigned long long* counters;
+  const int32_t* prim_index;  // input index of each sphere, quad and triangle slot (HostScene::prim_index)
+  const float4* edges;        // 3 per triangle slot: the edge records (null in a scene without triangles)
+  // stack entries beyond the LDS part: per wave [spill_depth][lane] codes, then [spill_depth][lane] bounds
+  int32_t* spill;
+  uint32_t num_points;   // < 2^31
+  int32_t spill_depth;   // entries per lane and stack in `spill` (0: the LDS stacks suffice)
+  int32_t lds_stack;     // entries per lane and stack kept in LDS (<= kLdsStack)
+  int32_t refill_batch;  // of 64 live lanes: finished lanes that start a write-out and refill pass
+  int32_t block;         // points a wave reserves from the cursor with one atomicAdd (a multiple of 64)
+  int32_t leaf_batch;    // run a leaf trip once this many lanes wait at a leaf
+  // schedule 3: byte offsets in dynamic LDS
+  int32_t lds_nodes, lds_stacks, lds_spheres, lds_quads, lds_edges, lds_refs;
 };
 
 }  // namespace rtg

@@ -28,6 +28,8 @@ RTG_MAT_LAMBERTIAN, RTG_MAT_METAL, RTG_MAT_DIELECTRIC, RTG_MAT_DIFFUSE_LIGHT = 1
 RTG_TEX_SOLID, RTG_TEX_CHECKER, RTG_TEX_IMAGE, RTG_TEX_NOISE = 1, 2, 3, 4
 RTG_BVH_MEDIAN, RTG_BVH_SAH, RTG_BVH_GPU = 0, 1, 3
 RTG_BVH_REFIT = 0x100  # or-ed into bvh_mode: the scene can be updated (DeviceScene.update)
+RTG_BVH_NEAREST = 0x200  # or-ed into bvh_mode: the scene answers DeviceScene.closest_point (triangle edge records)
+RTG_NEAREST_DEVICE = 0x2
 RTG_RENDER_OUT_DEVICE, RTG_RENDER_ASYNC, RTG_RENDER_COUNT = 0x1, 0x2, 0x4
 RTG_QUERY_ANY, RTG_QUERY_DEVICE, RTG_QUERY_ASYNC, RTG_QUERY_SORT = 0x1, 0x2, 0x4, 0x8
 RTG_QUERY_SORT_CHUNK = 4096
@@ -150,6 +152,25 @@ class rtg_query_stats(C.Structure):
                 ("reserved_", C.c_uint64 * 5)]
 
 
+class rtg_point(C.Structure):
+    _fields_ = [("p", C.c_float * 3), ("max_dist", C.c_float)]
+
+
+class rtg_nearest(C.Structure):
+    _fields_ = [("dist", C.c_float), ("prim", C.c_int32), ("u", C.c_float), ("v", C.c_float),
+                ("point", C.c_float * 3), ("side", C.c_int32)]
+
+
+class rtg_nearest_desc(C.Structure):
+    _fields_ = [("points", C.c_void_p), ("times", C.c_void_p), ("num_points", C.c_int64), ("out", C.c_void_p),
+                ("flags", C.c_int32), ("max_workgroups", C.c_int32), ("stream", C.c_void_p)]
+
+
+class rtg_nearest_stats(C.Structure):
+    _fields_ = [("points", C.c_uint64), ("found", C.c_uint64), ("kernel_ms", C.c_double),
+                ("reserved_", C.c_uint64 * 5)]
+
+
 class rtg_sort_layout(C.Structure):
     _fields_ = [("lo", C.c_float * 6), ("hi", C.c_float * 6), ("bits", C.c_int32 * 6), ("key_bits", C.c_int32),
                 ("empty", C.c_int32), ("chunk", C.c_int32), ("workgroups", C.c_int32), ("scene_extent", C.c_double)]
@@ -175,6 +196,9 @@ UPDATE_DTYPE = [("p0", "<f4", 3), ("radius", "<f4"), ("p1", "<f4", 3), ("pad0_",
 # numpy views of rtg_ray / rtg_hit (DeviceScene.intersect takes and returns these)
 RAY_DTYPE = [("origin", "<f4", 3), ("tmin", "<f4"), ("dir", "<f4", 3), ("tmax", "<f4")]
 HIT_DTYPE = [("t", "<f4"), ("prim", "<i4"), ("u", "<f4"), ("v", "<f4"), ("normal", "<f4", 3), ("front_face", "<i4")]
+# numpy views of rtg_point / rtg_nearest (DeviceScene.closest_point takes and returns these)
+POINT_DTYPE = [("p", "<f4", 3), ("max_dist", "<f4")]
+NEAREST_DTYPE = [("dist", "<f4"), ("prim", "<i4"), ("u", "<f4"), ("v", "<f4"), ("point", "<f4", 3), ("side", "<i4")]
 
 
 class rtg_bvh_node_host(C.Structure):
@@ -197,7 +221,7 @@ RTG_SYMBOLS = ("rtg_abi_version", "rtg_last_error", "rtg_device_count", "rtg_cam
                "rtg_shard_layout", "rtg_deinterleave_rows_host", "rtg_scene_prepare",
                "rtg_hot_treelet_order_host", "rtg_bvh_node_order",
                "rtg_allocation_count", "rtg_intersect", "rtg_scene_update",
-               "rtg_ray_sort_keys_host", "rtg_query_last_order")
+               "rtg_ray_sort_keys_host", "rtg_query_last_order", "rtg_closest_point")
 RTG_COMM_ID_BYTES = 128
 
 
@@ -284,6 +308,7 @@ class Library:
         L.rtg_allocation_count.argtypes = [_P(C.c_uint64), _P(C.c_uint64)]
         L.rtg_intersect.argtypes = [C.c_void_p, _P(rtg_query_desc), _P(rtg_query_stats)]
         L.rtg_scene_update.argtypes = [C.c_void_p, _P(rtg_update_desc), _P(rtg_update_stats)]
+        L.rtg_closest_point.argtypes = [C.c_void_p, _P(rtg_nearest_desc), _P(rtg_nearest_stats)]
         L.rtg_ray_sort_keys_host.argtypes = [C.c_void_p, C.c_int64, C.c_double, C.c_void_p, _P(rtg_sort_layout)]
         L.rtg_query_last_order.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, _P(C.c_int64),
                                            _P(rtg_sort_layout)]
@@ -293,7 +318,7 @@ class Library:
                      "rtg_comm_create_rank", "rtg_comm_size", "rtg_gather_rows", "rtg_deinterleave_rows",
                      "rtg_render_frame", "rtg_render_plan", "rtg_shard_layout", "rtg_deinterleave_rows_host",
                      "rtg_bvh_node_order", "rtg_allocation_count", "rtg_intersect", "rtg_scene_update",
-                     "rtg_ray_sort_keys_host", "rtg_query_last_order"):
+                     "rtg_ray_sort_keys_host", "rtg_query_last_order", "rtg_closest_point"):
             getattr(L, name).restype = C.c_int32
         if L.rtg_abi_version() != RTG_ABI_VERSION:
             raise RuntimeError("librtgpu ABI version mismatch")
@@ -585,6 +610,39 @@ class DeviceScene:
                            C.c_void_p(stream_ptr) if stream_ptr else None)
         st = rtg_query_stats()
         self.L.check("rtg_intersect", self.L.lib.rtg_intersect(self.handle, C.byref(q), C.byref(st)))
+        return st
+
+    def closest_point(self, points, times=None, schedule: int = 0, max_workgroups: int = 0, out=None):
+        """Batched nearest-surface query (rtgpu.h rtg_closest_point; scenes created with RTG_BVH_NEAREST): `points` a
+        numpy array of POINT_DTYPE, `times` float32 per point or None; returns (out, stats), out a numpy array of
+        NEAREST_DTYPE. out: a contiguous NEAREST_DTYPE array of the batch's length to fill instead of a new one."""
+        import numpy as np
+
+        points = np.ascontiguousarray(points, dtype=np.dtype(POINT_DTYPE))
+        if out is None:
+            out = np.zeros(points.shape[0], dtype=np.dtype(NEAREST_DTYPE))
+        elif out.dtype != np.dtype(NEAREST_DTYPE) or out.shape != points.shape or not out.flags.c_contiguous:
+            raise ValueError("out must be a contiguous NEAREST_DTYPE array with one record per point")
+        if times is not None:
+            times = np.ascontiguousarray(times, dtype=np.float32)
+            if times.shape != (points.shape[0],):
+                raise ValueError("times must hold one float per point")
+        q = rtg_nearest_desc(points.ctypes.data, times.ctypes.data if times is not None else None, points.shape[0],
+                             out.ctypes.data, RTG_RENDER_SCHEDULE(schedule), max_workgroups, None)
+        st = rtg_nearest_stats()
+        self.L.check("rtg_closest_point", self.L.lib.rtg_closest_point(self.handle, C.byref(q), C.byref(st)))
+        return out, st
+
+    def closest_point_device(self, points_ptr: int, num_points: int, out_ptr: int, times_ptr: int = 0,
+                             stream_ptr: Optional[int] = None, schedule: int = 0,
+                             max_workgroups: int = 0) -> rtg_nearest_stats:
+        """The same on device memory of the scene's device (16-byte rtg_point, 32-byte rtg_nearest records), on
+        `stream_ptr` (hipStream_t); blocking."""
+        q = rtg_nearest_desc(C.c_void_p(points_ptr), C.c_void_p(times_ptr) if times_ptr else None, num_points,
+                             C.c_void_p(out_ptr), RTG_NEAREST_DEVICE | RTG_RENDER_SCHEDULE(schedule), max_workgroups,
+                             C.c_void_p(stream_ptr) if stream_ptr else None)
+        st = rtg_nearest_stats()
+        self.L.check("rtg_closest_point", self.L.lib.rtg_closest_point(self.handle, C.byref(q), C.byref(st)))
         return st
 
     def query_last_order(self):
