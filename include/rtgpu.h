@@ -593,6 +593,39 @@ typedef struct rtg_nearest_stats {
 } rtg_nearest_stats;
 rtg_status rtg_closest_point(rtg_scene* scene, const rtg_nearest_desc* q, rtg_nearest_stats* stats);
 
+/* ---- k nearest surfaces per point (additive in ABI 7) ----
+ * rtg_closest_points answers each point with up to k primitives: everything rtg_closest_point documents, plus:
+ *  - Candidates of point i: the primitives with dist <= max_dist (sqrtf of the fp32 squared distance; the walk's
+ *    bound is max_dist^2 rounded up). The answer is the min(k, #candidates) candidates smallest in the order
+ *    (squared-distance bits, input index), written to out[i*k .. i*k+count) in that order: at bit-equal squared
+ *    distance the lower input index comes first, and a primitive appears at most once. The remaining k - count
+ *    records are the miss record (dist -1, prim -1, rest 0); counts[i] = count (counts may be NULL). Each record is
+ *    exactly what rtg_closest_point would write for that primitive, and with k == 1 the output is byte-identical to
+ *    rtg_closest_point's. An invalid point (as defined there) gets k miss records and count 0.
+ *  - Pruning is conservative with the same bound expression, applied to the k-th best squared distance once k
+ *    candidates are held and to the radius bound until then; the sphere kept out of the BVH is an ordinary
+ *    candidate, tested first. The output depends on the point, the time, the records and the input indices only.
+ *  - stats: points, found = the sum of the counts; reserved_[0..3] as for rtg_closest_point, reserved_[4] = k.
+ *  - The descriptor is checked first: NULL, a negative count, unknown flags, NULL points / out with a count above
+ *    0, k < 1 are RTG_E_INVALID; k > RTG_NEAREST_K_MAX, num_points * k >= 2^31, schedule 5, a schedule the scene
+ *    cannot run (the lists share the LDS with the scene) and a triangle scene without RTG_BVH_NEAREST are
+ *    RTG_E_UNSUPPORTED. num_points == 0 is RTG_OK and launches nothing.
+ *  - Blocking; host batches go through the scene's grow-only staging (the results' part grows to num_points * k
+ *    records): steady-state calls allocate nothing. Waits for a ray query still in flight. */
+#define RTG_NEAREST_K_MAX 16
+typedef struct rtg_nearest_k_desc {
+  const rtg_point* points;
+  const float* times; /* one per point, or NULL: 0 for every point */
+  int64_t num_points;
+  int32_t k;     /* 1..RTG_NEAREST_K_MAX */
+  int32_t flags; /* RTG_NEAREST_DEVICE | RTG_RENDER_SCHEDULE(n), as rtg_nearest_desc.flags */
+  rtg_nearest* out; /* num_points * k records, point-major */
+  int32_t* counts;  /* num_points entries, or NULL */
+  int32_t max_workgroups; /* 0: library default */
+  void* stream;           /* hipStream_t, NULL: the scene's own stream */
+} rtg_nearest_k_desc;
+rtg_status rtg_closest_points(rtg_scene* scene, const rtg_nearest_k_desc* q, rtg_nearest_stats* stats);
+
 /* ---- multi-GPU frames: row-interleaved shards, one RCCL gather over xGMI ----
  * Replaces the reference's single-device pixel loop of camera::render (camera.hpp:29-72) when the
  * image is tiled over several GPUs: rank r renders rows r, r+N, r+2N, ... (any N gives the same

@@ -48,6 +48,12 @@ hipError_t launch_nearest(const KernelChoice& k, const DevScene& S, const DevNea
                           hipStream_t stream);
 hipError_t launch_update_edges(const int32_t* indices, const float4* prims, int64_t count, int64_t num_prims,
                                const int32_t* slot_of, float4* edges, int64_t num_tris, hipStream_t stream);
+// rtg_nearest_k.hip
+KernelChoice choose_nearest_k_kernel(const DevScene& S, int variant, bool spill);
+int nearest_k_lds_layout(const DevScene& S, int waves, int entries, int k, DevNearestK* K);
+int nearest_k_grid_lds(int k, DevNearestK* K);
+hipError_t launch_nearest_k(const KernelChoice& k, const DevScene& S, const DevNearestK& K, int lds_bytes,
+                            int grid_blocks, hipStream_t stream);
 }  // namespace rtg
 
 using namespace rtg;
@@ -2807,6 +2813,192 @@ rtg_status rtg_closest_point(rtg_scene* s, const rtg_nearest_desc* q, rtg_neares
   if (c[0] != static_cast<unsigned long long>(n))
     return fail(RTG_E_HIP, "the query answered " + std::to_string(c[0]) + " of " + std::to_string(n) + " points");
   if (!dev) std::memcpy(q->out, s->host_stage, out_bytes);
+  return RTG_OK;
+}
+
+rtg_status rtg_closest_points(rtg_scene* s, const rtg_nearest_k_desc* q, rtg_nearest_stats* stats) {
+  // the descriptor first, then the scene (rtgpu.h), in rtg_closest_point's order
+  if (!q) return fail(RTG_E_INVALID, "null query descriptor");
+  if (stats) *stats = rtg_nearest_stats{};
+  if (q->num_points < 0) return fail(RTG_E_INVALID, "num_points is negative");
+  if (q->flags & ~(RTG_NEAREST_DEVICE | 0xff00)) return fail(RTG_E_INVALID, "unknown query flags");
+  if (q->max_workgroups < 0) return fail(RTG_E_INVALID, "max_workgroups is negative");
+  if (q->num_points > 0 && (!q->points || !q->out)) return fail(RTG_E_INVALID, "null point or result array");
+  if (q->k < 1) return fail(RTG_E_INVALID, "k is below 1");
+  if (q->k > RTG_NEAREST_K_MAX) return fail(RTG_E_UNSUPPORTED, "k is above RTG_NEAREST_K_MAX");
+  if (q->num_points > ((int64_t(1) << 31) - 1) / q->k)
+    return fail(RTG_E_UNSUPPORTED, "num_points * k must be below 2^31 (split the batch)");
+  if (!s) return fail(RTG_E_INVALID, "null scene");
+  if (s->pending) return fail(RTG_E_INVALID, "a previous async render was not waited for");
+  const bool dev = (q->flags & RTG_NEAREST_DEVICE) != 0;
+  const int k = q->k;
+  int variant = (q->flags >> 8) & 0xff;
+  if (variant == 5) return fail(RTG_E_UNSUPPORTED, "proximity queries have no treelet schedule");
+  if (variant != 0 && variant != 3 && variant != 4) return fail(RTG_E_INVALID, "unknown query schedule");
+  if (s->dev.num_tris > 0 && !s->tri_edges)
+    return fail(RTG_E_UNSUPPORTED, "the scene has triangles and was created without RTG_BVH_NEAREST");
+  if (s->prim_index.empty() && s->dev.num_refs + (s->dev.occluder >= 0 ? 1 : 0) > 0)
+    return fail(RTG_E_UNSUPPORTED, "proximity queries need fewer than 2^31 primitives");
+  RTG_HIP(hipSetDevice(s->device), "hipSetDevice");
+  rtg_status st = finish_query(s);
+  if (st != RTG_OK) return st;
+
+  // ---- the launch plan: rtg_closest_point's, with the lists in every kernel's LDS (k x 512 B per wave)
+  const Knobs& K = s->knobs;
+  const int need = std::max(1, s->stack_need);
+  int entries = K.stack_lds_entries > 0 ? std::min(kLdsStack, K.stack_lds_entries) : kLdsStack;
+  const bool spill = need > entries;
+  if (!spill) entries = kLdsStack;  // the LdsStack kernel's layout
+  DevScene dscene = s->dev;
+  dscene.node_visits = nullptr;
+  DevNearestK dk{};
+  dk.k = k;
+  DevNearest& dn = dk.q;
+  auto waves_per_simd = [](const KernelChoice& kc) {  // 512 registers per lane, granule 8
+    const KernelResources r = kernel_resources(kc.fn);
+    return r.ok && r.vgprs > 0 ? std::max(1, std::min(8, 512 / ((r.vgprs + 7) / 8 * 8))) : 4;
+  };
+  KernelChoice kc;
+  int lds_bytes = 0, wgs_per_cu = 1, waves = 4;
+  if (variant == 0 || variant == 3) {
+    kc = choose_nearest_k_kernel(dscene, 3, spill);
+    int best = 0;
+    if (kc.fn) {
+      const int wps = waves_per_simd(kc);
+      for (const int w : {16, 8, 4}) {  // the shape with the most resident waves; ties to the larger workgroup
+        const int b = nearest_k_lds_layout(dscene, w, entries, k, nullptr);
+        if (b < 0) continue;
+        const int g = std::min(kLdsPerCu / lds_alloc(b), wps * 4 / w);
+        if (g * w > best) best = g * w, waves = w, wgs_per_cu = g;
+      }
+    }
+    if (best > 0) {
+      variant = 3;
+      lds_bytes = nearest_k_lds_layout(dscene, waves, entries, k, &dk);
+    } else if (variant == 3) {
+      return fail(RTG_E_UNSUPPORTED,
+                  "scene does not fit the LDS proximity schedule with its lists (or its tree is not 4-wide)");
+    } else {
+      variant = 4;
+    }
+  }
+  if (variant == 4) {
+    kc = choose_nearest_k_kernel(dscene, 4, spill);
+    waves = 4;
+    lds_bytes = nearest_k_grid_lds(k, &dk);
+    wgs_per_cu = std::max(1, std::min(waves_per_simd(kc), kLdsPerCu / lds_alloc(lds_bytes)));
+  }
+  if (!kc.fn) return fail(RTG_E_UNSUPPORTED, "no proximity kernel fits this scene");
+  kc.block = waves * 64;
+  if (stats) {
+    stats->reserved_[0] = static_cast<uint64_t>(variant);
+    stats->reserved_[2] = static_cast<uint64_t>(waves);
+    stats->reserved_[3] = static_cast<uint64_t>(lds_bytes);
+    stats->reserved_[4] = static_cast<uint64_t>(k);
+  }
+  if (q->num_points == 0) return RTG_OK;  // nothing to launch
+  const int64_t n = q->num_points;
+  int64_t grid = int64_t(s->num_cus) * wgs_per_cu;
+  if (q->max_workgroups > 0) grid = std::min<int64_t>(grid, q->max_workgroups);
+  grid = std::max<int64_t>(1, std::min(grid, (n + kc.block - 1) / kc.block));  // what the points can fill
+  if (stats) stats->reserved_[1] = static_cast<uint64_t>(grid);
+  dn.num_points = static_cast<uint32_t>(n);
+  dn.lds_stack = entries;
+  dn.spill_depth = std::max(0, need - entries);
+  dn.refill_batch = K.query_refill;
+  dn.block = static_cast<int32_t>(std::max<int64_t>(64, std::min<int64_t>(512, n / (grid * waves * 8) / 64 * 64)));
+  dn.leaf_batch = s->dev.num_nodes <= kSmallBvhNodes ? kSmallBvhLeafBatch : kDefaultLeafBatch;  // the ray query's
+  dn.edges = s->tri_edges;
+
+  hipStream_t stream = q->stream ? static_cast<hipStream_t>(q->stream) : s->own_stream;
+  SyncOnError sync_on_error;
+  sync_on_error.stream = stream;
+  auto grow = [](ScratchBuf& b, size_t bytes, const char* what) -> rtg_status {
+    if (b.p && b.bytes >= bytes) return RTG_OK;
+    if (b.p) RTG_HIP(hipFree(b.p), "hipFree(scratch)");  // device-synchronous: nothing still reads it
+    b.p = nullptr;
+    b.bytes = 0;
+    RTG_HIP(dev_alloc(&b.p, std::max<size_t>(bytes, 256)), what);
+    b.bytes = bytes;
+    return RTG_OK;
+  };
+  if (!s->prim_index_dev && !s->prim_index.empty()) {  // the scene's first query of any kind
+    RTG_HIP(dev_alloc(reinterpret_cast<void**>(&s->prim_index_dev), s->prim_index.size() * 4), "hipMalloc(prim index)");
+    RTG_HIP(hipMemcpy(s->prim_index_dev, s->prim_index.data(), s->prim_index.size() * 4, hipMemcpyHostToDevice),
+            "hipMemcpy(prim index)");
+  }
+  dn.prim_index = s->prim_index_dev;
+  dn.counters = s->counters;
+  const size_t point_bytes = static_cast<size_t>(n) * sizeof(rtg_point);
+  const size_t out_bytes = static_cast<size_t>(n) * k * sizeof(rtg_nearest), count_bytes = static_cast<size_t>(n) * 4;
+  const size_t time_bytes = q->times ? static_cast<size_t>(n) * 4 : 0;
+  if (dev) {
+    dn.points = reinterpret_cast<const float4*>(q->points);
+    dn.times = q->times;
+    dn.out = reinterpret_cast<float4*>(q->out);
+    dk.counts = q->counts;
+  } else {
+    // pinned staging (the scene's host_stage), then one DMA each way; results | counts | points | times on the
+    // device (32 k + 4 bytes per point: the points' part stays 4-byte aligned only, so it is rounded up to 16)
+    const size_t head = (out_bytes + count_bytes + 15) & ~size_t(15);
+    const size_t stage_bytes = std::max(out_bytes + count_bytes, point_bytes + time_bytes);
+    if (s->host_stage_bytes < stage_bytes) {
+      if (s->host_stage) RTG_HIP(hipHostFree(s->host_stage), "hipHostFree(stage)");
+      s->host_stage = nullptr;
+      s->host_stage_bytes = 0;
+      RTG_HIP(host_alloc(&s->host_stage, stage_bytes), "hipHostMalloc(stage)");
+      s->host_stage_bytes = stage_bytes;
+    }
+    st = grow(s->scr_query, head + point_bytes + static_cast<size_t>(n) * 4, "hipMalloc(query staging)");
+    if (st != RTG_OK) return st;
+    char* stage = static_cast<char*>(s->host_stage);
+    std::memcpy(stage, q->points, point_bytes);
+    if (q->times) std::memcpy(stage + point_bytes, q->times, time_bytes);
+    char* dbase = static_cast<char*>(s->scr_query.p);
+    RTG_HIP(hipMemcpyAsync(dbase + head, stage, point_bytes + time_bytes, hipMemcpyHostToDevice, stream),
+            "hipMemcpy(points)");
+    dn.out = reinterpret_cast<float4*>(dbase);
+    dk.counts = reinterpret_cast<int32_t*>(dbase + out_bytes);
+    dn.points = reinterpret_cast<const float4*>(dbase + head);
+    dn.times = q->times ? reinterpret_cast<const float*>(dbase + head + point_bytes) : nullptr;
+  }
+  dn.spill = nullptr;
+  if (dn.spill_depth > 0) {  // the render's spill area, two stacks deep (queries and renders of a scene never overlap)
+    st = grow(s->scr_spill, static_cast<size_t>(grid) * waves * 64 * dn.spill_depth * 2 * sizeof(int32_t), "hipMalloc(stack spill)");
+    if (st != RTG_OK) return st;
+    dn.spill = static_cast<int32_t*>(s->scr_spill.p);
+  }
+  if (K.verbose)
+    std::fprintf(stderr, "[rtg] k-nearest (k = %d) schedule %d: %lld workgroups of %d waves (%d per CU), %d B LDS, stacks %d + %d\n",
+                 k, variant, static_cast<long long>(grid), waves, wgs_per_cu, lds_bytes, dn.lds_stack, dn.spill_depth);
+  RTG_HIP(hipMemsetAsync(s->counters, 0, kNumCounters * sizeof(unsigned long long), stream), "hipMemsetAsync");
+  RTG_HIP(hipEventRecord(s->ev0, stream), "hipEventRecord");
+  RTG_HIP(launch_nearest_k(kc, dscene, dk, lds_bytes, static_cast<int>(grid), stream), "k-nearest kernel launch");
+  RTG_HIP(hipEventRecord(s->ev1, stream), "hipEventRecord");
+  RTG_HIP(hipMemcpyAsync(s->host_counters, s->counters, kNumCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                         stream),
+          "hipMemcpyAsync(counters)");
+  // results and counts lie back to back on the device: one DMA
+  if (!dev) RTG_HIP(hipMemcpyAsync(s->host_stage, dn.out, out_bytes + count_bytes, hipMemcpyDeviceToHost, stream), "hipMemcpy(results)");
+  sync_on_error.committed = true;
+  RTG_HIP(hipStreamSynchronize(stream), "k-nearest kernel");
+  const unsigned long long* c = s->host_counters;
+  float ms = 0.0f;
+  RTG_HIP(hipEventElapsedTime(&ms, s->ev0, s->ev1), "hipEventElapsedTime");
+  if (stats) {
+    stats->points = c[0];
+    stats->found = c[3];
+    stats->kernel_ms = ms;
+  }
+  if (c[4] != 0)
+    return fail(RTG_E_UNSUPPORTED, "BVH traversal stack overflow in " + std::to_string(c[4]) + " waves (proximity query)");
+  if (c[5] != 0) return fail(RTG_E_INVALID, "corrupt BVH child code met during a proximity query's traversal");
+  if (c[0] != static_cast<unsigned long long>(n))
+    return fail(RTG_E_HIP, "the query answered " + std::to_string(c[0]) + " of " + std::to_string(n) + " points");
+  if (!dev) {
+    std::memcpy(q->out, s->host_stage, out_bytes);
+    if (q->counts) std::memcpy(q->counts, static_cast<char*>(s->host_stage) + out_bytes, count_bytes);
+  }
   return RTG_OK;
 }
 

@@ -410,4 +410,13 @@ struct DevNearest {
   int32_t lds_nodes, lds_stacks, lds_spheres, lds_quads, lds_edges, lds_refs;
 };
 
+// One k-nearest launch (rtg_closest_points; kernels in rtg_nearest_k.hip), passed by value after the DevScene: the
+// proximity launch (q.out holds k records per point, point-major) and the candidate lists.
+struct DevNearestK {
+  DevNearest q;
+  int32_t* counts;    // one per point: the records that are not miss records, or null
+  int32_t k;          // records per point, 1..RTG_NEAREST_K_MAX
+  int32_t lds_lists;  // byte offset of the candidate lists in dynamic LDS: per wave [2 k][lane] words
+};
+
 }  // namespace rtg

@@ -30,6 +30,7 @@ RTG_BVH_MEDIAN, RTG_BVH_SAH, RTG_BVH_GPU = 0, 1, 3
 RTG_BVH_REFIT = 0x100  # or-ed into bvh_mode: the scene can be updated (DeviceScene.update)
 RTG_BVH_NEAREST = 0x200  # or-ed into bvh_mode: the scene answers DeviceScene.closest_point (triangle edge records)
 RTG_NEAREST_DEVICE = 0x2
+RTG_NEAREST_K_MAX = 16  # DeviceScene.closest_points: the most records per point
 RTG_RENDER_OUT_DEVICE, RTG_RENDER_ASYNC, RTG_RENDER_COUNT = 0x1, 0x2, 0x4
 RTG_QUERY_ANY, RTG_QUERY_DEVICE, RTG_QUERY_ASYNC, RTG_QUERY_SORT = 0x1, 0x2, 0x4, 0x8
 RTG_QUERY_SORT_CHUNK = 4096
@@ -166,6 +167,12 @@ class rtg_nearest_desc(C.Structure):
                 ("flags", C.c_int32), ("max_workgroups", C.c_int32), ("stream", C.c_void_p)]
 
 
+class rtg_nearest_k_desc(C.Structure):
+    _fields_ = [("points", C.c_void_p), ("times", C.c_void_p), ("num_points", C.c_int64), ("k", C.c_int32),
+                ("flags", C.c_int32), ("out", C.c_void_p), ("counts", C.c_void_p), ("max_workgroups", C.c_int32),
+                ("stream", C.c_void_p)]
+
+
 class rtg_nearest_stats(C.Structure):
     _fields_ = [("points", C.c_uint64), ("found", C.c_uint64), ("kernel_ms", C.c_double),
                 ("reserved_", C.c_uint64 * 5)]
@@ -221,7 +228,7 @@ RTG_SYMBOLS = ("rtg_abi_version", "rtg_last_error", "rtg_device_count", "rtg_cam
                "rtg_shard_layout", "rtg_deinterleave_rows_host", "rtg_scene_prepare",
                "rtg_hot_treelet_order_host", "rtg_bvh_node_order",
                "rtg_allocation_count", "rtg_intersect", "rtg_scene_update",
-               "rtg_ray_sort_keys_host", "rtg_query_last_order", "rtg_closest_point")
+               "rtg_ray_sort_keys_host", "rtg_query_last_order", "rtg_closest_point", "rtg_closest_points")
 RTG_COMM_ID_BYTES = 128
 
 
@@ -309,6 +316,7 @@ class Library:
         L.rtg_intersect.argtypes = [C.c_void_p, _P(rtg_query_desc), _P(rtg_query_stats)]
         L.rtg_scene_update.argtypes = [C.c_void_p, _P(rtg_update_desc), _P(rtg_update_stats)]
         L.rtg_closest_point.argtypes = [C.c_void_p, _P(rtg_nearest_desc), _P(rtg_nearest_stats)]
+        L.rtg_closest_points.argtypes = [C.c_void_p, _P(rtg_nearest_k_desc), _P(rtg_nearest_stats)]
         L.rtg_ray_sort_keys_host.argtypes = [C.c_void_p, C.c_int64, C.c_double, C.c_void_p, _P(rtg_sort_layout)]
         L.rtg_query_last_order.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, _P(C.c_int64),
                                            _P(rtg_sort_layout)]
@@ -318,7 +326,7 @@ class Library:
                      "rtg_comm_create_rank", "rtg_comm_size", "rtg_gather_rows", "rtg_deinterleave_rows",
                      "rtg_render_frame", "rtg_render_plan", "rtg_shard_layout", "rtg_deinterleave_rows_host",
                      "rtg_bvh_node_order", "rtg_allocation_count", "rtg_intersect", "rtg_scene_update",
-                     "rtg_ray_sort_keys_host", "rtg_query_last_order", "rtg_closest_point"):
+                     "rtg_ray_sort_keys_host", "rtg_query_last_order", "rtg_closest_point", "rtg_closest_points"):
             getattr(L, name).restype = C.c_int32
         if L.rtg_abi_version() != RTG_ABI_VERSION:
             raise RuntimeError("librtgpu ABI version mismatch")
@@ -643,6 +651,47 @@ class DeviceScene:
                              C.c_void_p(stream_ptr) if stream_ptr else None)
         st = rtg_nearest_stats()
         self.L.check("rtg_closest_point", self.L.lib.rtg_closest_point(self.handle, C.byref(q), C.byref(st)))
+        return st
+
+    def closest_points(self, points, k: int, times=None, schedule: int = 0, max_workgroups: int = 0, out=None,
+                       counts=None):
+        """The k nearest surfaces per point (rtgpu.h rtg_closest_points), sorted by (distance, input index): returns
+        (records, counts, stats), records a NEAREST_DTYPE array of shape (n, k) whose row i holds counts[i] records
+        and then miss records, counts int32 of shape (n,). out / counts: contiguous arrays of those shapes to fill
+        instead of new ones."""
+        import numpy as np
+
+        points = np.ascontiguousarray(points, dtype=np.dtype(POINT_DTYPE))
+        n = points.shape[0]
+        if out is None:
+            out = np.zeros((n, max(k, 0)), dtype=np.dtype(NEAREST_DTYPE))
+        elif out.dtype != np.dtype(NEAREST_DTYPE) or out.shape != (n, k) or not out.flags.c_contiguous:
+            raise ValueError("out must be a contiguous NEAREST_DTYPE array of shape (points, k)")
+        if counts is None:
+            counts = np.zeros(n, dtype=np.int32)
+        elif counts.dtype != np.int32 or counts.shape != (n,) or not counts.flags.c_contiguous:
+            raise ValueError("counts must be a contiguous int32 array with one entry per point")
+        if times is not None:
+            times = np.ascontiguousarray(times, dtype=np.float32)
+            if times.shape != (n,):
+                raise ValueError("times must hold one float per point")
+        q = rtg_nearest_k_desc(points.ctypes.data, times.ctypes.data if times is not None else None, n, k,
+                               RTG_RENDER_SCHEDULE(schedule), out.ctypes.data, counts.ctypes.data, max_workgroups, None)
+        st = rtg_nearest_stats()
+        self.L.check("rtg_closest_points", self.L.lib.rtg_closest_points(self.handle, C.byref(q), C.byref(st)))
+        return out, counts, st
+
+    def closest_points_device(self, points_ptr: int, num_points: int, k: int, out_ptr: int, counts_ptr: int = 0,
+                              times_ptr: int = 0, stream_ptr: Optional[int] = None, schedule: int = 0,
+                              max_workgroups: int = 0) -> rtg_nearest_stats:
+        """The same on device memory of the scene's device (num_points * k 32-byte records, point-major; int32
+        counts or 0 for none), on `stream_ptr` (hipStream_t); blocking."""
+        q = rtg_nearest_k_desc(C.c_void_p(points_ptr), C.c_void_p(times_ptr) if times_ptr else None, num_points, k,
+                               RTG_NEAREST_DEVICE | RTG_RENDER_SCHEDULE(schedule), C.c_void_p(out_ptr),
+                               C.c_void_p(counts_ptr) if counts_ptr else None, max_workgroups,
+                               C.c_void_p(stream_ptr) if stream_ptr else None)
+        st = rtg_nearest_stats()
+        self.L.check("rtg_closest_points", self.L.lib.rtg_closest_points(self.handle, C.byref(q), C.byref(st)))
         return st
 
     def query_last_order(self):

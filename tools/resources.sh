@@ -23,6 +23,11 @@ if [ -n "${RES_NEAREST:-}" ]; then
   src=rtg_nearest.hip
   extra="-fPIC -Xclang -target-feature -Xclang -packed-fp32-ops"
 fi
+# RES_NEAREST_K=1: the k-nearest kernels (rtg_nearest_k.hip), the same flags
+if [ -n "${RES_NEAREST_K:-}" ]; then
+  src=rtg_nearest_k.hip
+  extra="-fPIC -Xclang -target-feature -Xclang -packed-fp32-ops"
+fi
 /opt/rocm/bin/hipcc -std=c++17 -O3 --offload-arch=gfx950 -ffp-contract=off -fno-slp-vectorize -Iinclude \
   -Iraytracing-practice_amd/csrc ${RES_DEFS:-} $extra -c raytracing-practice_amd/csrc/$src -o /tmp/rtg_res.o \
   -Rpass-analysis=kernel-resource-usage 2>&1 |
